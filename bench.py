@@ -11,8 +11,12 @@ semantics).  A "step" aligns one batch of `--pairs` document pairs per GPU, inpu
 resident in HBM.  Workload `c3` (configs[2]): `--pairs` ragged pairs per GPU, N, M ~ U{512..8192}.  Document pairs
 are independent, so ranks share nothing: weak scaling, no data-path collective (RCCL only for the timing barrier).
 
-Prints ONE JSON line:
-  value           aligned doc-pairs/s, whole job, inputs resident in HBM;
+A plain run sets up, warms up, times `--steps` steps, writes the outputs of the last timed step when
+`--dump-outputs DIR` is given, and prints ONE JSON line: value (aligned doc-pairs/s, whole job, inputs resident in
+HBM), ms_per_step (one timed step), config and the other fields that cost nothing to compute.  Everything else below
+(per-stage timers, roofline, parity, end-to-end and CPU legs, the other workloads) is measured only with `--full`.
+
+With `--full` the line also holds:
   roofline        the dominant kernel (by rocprof symbol = one stage timer) against HBM peak.  `achieved` follows
                   SURVEY.md 8(d): compulsory bytes K(N+M)d*e per pair x pairs per launch / the kernel's average
                   launch time (HIP events on the launch stream, timed region).  `own_pass` is the same kernel
@@ -101,6 +105,32 @@ def synth_pairs_device(N, M, K, d, seeds, dev, dtype):
 
 def synth_pair_device(N, M, K, d, seed, dev, dtype):
     return synth_pairs_device(N, M, K, d, [seed], dev, dtype)[0]
+
+
+def dump_outputs(pb, path, sample=128):
+    """--dump-outputs: what PreparedBatch.results() hands a caller for the last timed step, as float64 .npy files.
+    Every pair: alignment_count, score_sum, del_penalty [P][levels] (zero past a pair's own levels).  A fixed seeded
+    sample of `sample` pairs (sample_pairs): their alignment rows (x_start, x_len, y_start, y_len), sample_rows, and
+    their scores, sample_scores, concatenated pair after pair (sample_counts rows each)."""
+    info, rows, scores, pens, offs = pb.raw_results()
+    P = len(pb.vecs)
+    cnt = info[:, 0].astype(np.int64)
+    pick = np.sort(np.random.RandomState(0).choice(P, min(P, sample), replace=False))
+    pen = np.zeros((P, max(pb.levels)), np.float64)
+    for i, lv in enumerate(pb.levels):
+        pen[i, :lv] = pens[i, :lv]
+    out = {
+        "alignment_count": cnt,
+        "score_sum": np.array([scores[o:o + c].sum() for o, c in zip(offs[:P], cnt)]),
+        "del_penalty": pen,
+        "sample_pairs": pick,
+        "sample_counts": cnt[pick],
+        "sample_rows": np.concatenate([rows[offs[i]:offs[i] + cnt[i]] for i in pick]).reshape(-1, 4),
+        "sample_scores": np.concatenate([scores[offs[i]:offs[i] + cnt[i]] for i in pick]),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def level_sizes(N, M, max_full=300):
@@ -335,7 +365,8 @@ def bench_straight(args):
     for _ in range(args.warmup):
         pb.run()
     torch.cuda.synchronize()
-    lib.svx_set_profiling(ctx.h, 2)   # accumulate: events around every stage, read once after the timed steps
+    if args.full:
+        lib.svx_set_profiling(ctx.h, 2)   # accumulate: events around every stage, read once after the timed steps
     names = ["pyr0", "pyr_aux", "knob_sort", "knob_scores0", "knob", "path0", "tiles", "traceback0", "setup", "total"]
     ms = {k: 0.0 for k in names}
     if dist is not None:
@@ -349,14 +380,17 @@ def bench_straight(args):
         dist.barrier()
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    for k in names:
-        ms[k] = lib.svx_stage_ms(ctx.h, k.encode())
+    if args.full:
+        for k in names:
+            ms[k] = lib.svx_stage_ms(ctx.h, k.encode())
     if dist is not None:
         tt = torch.tensor([elapsed], device=rdev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     lib.svx_set_profiling(ctx.h, 0)
-    res = pb.results()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pb, args.dump_outputs)
+    res = pb.results() if args.full else []
     ok = all([x for al in r[0] for x in al[0]] == list(range(N)) and [y for al in r[0] for y in al[1]] == list(range(M)) for r in res)
     B = 2 * W
     # DP nodes inside the band and the lattice: sum over node diagonals of the overlap of [bo, bo + B) with the lattice
@@ -376,7 +410,9 @@ def bench_straight(args):
                                    "dense search (band %d covers the whole lattice)" % B) + ", %d doc-pairs per GPU per step" % P,
                       "name": args.workload, "pairs_per_step_per_gpu": P, "N": N, "M": M, "d": d, "overlaps": K, "band": B,
                       "parallelism": "dp%d (pairs sharded, no collective)" % world},
-           "seconds_per_pair": elapsed / (P * args.steps), "dp_cells_per_pair": nodes, "dp_cells_per_s": value * nodes,
+           "seconds_per_pair": elapsed / (P * args.steps), "dp_cells_per_pair": nodes, "dp_cells_per_s": value * nodes}
+    if args.full:
+        out.update({
            "alignments_cover_both_documents": bool(ok),
            "stage_ms_per_step": {k: v / args.steps for k, v in ms.items()},
            "roofline": {"bound": "mfma", "kernel": "k_band_tiles (cost tiles + DP wavefront)", "stage": "tiles",
@@ -385,7 +421,7 @@ def bench_straight(args):
                         "traffic_source": "no counter pass committed for this mode (the tile sweep re-reads its rows out of L2: DESIGN.md section 6)",
                         "avg_launch_ms": tile_ms, "algorithmic_flops_per_launch": flops * P,
                         "note": "the sweep is bound by the serial chain of tile anti-diagonals (%d of them) and the float64 DP inside a tile, "
-                                "not by the matrix cores" % ((N // 32 + 1) + (M // 32 + 1) - 1)}}
+                                "not by the matrix cores" % ((N // 32 + 1) + (M // 32 + 1) - 1)}})
     del pb, docs
     torch.cuda.empty_cache()
     return out if rank == 0 else None
@@ -433,7 +469,15 @@ def main():
                     "per step) and the dense mode, reported under `workloads`; 0 = skip")
     ap.add_argument("--pipeline", type=int, default=1, help="software pipeline over consecutive steps (svx_set_pipeline): the latency-bound "
                     "refinement chain of one half-batch runs beside the streaming passes of the other; 0 = every step runs start to end on one stream")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: per-stage timers and "
+                    "roofline, parity with the CPU oracle, CPU baselines, end-to-end legs, the other workloads (the --cpu_*, --e2e_*, "
+                    "--no_profile and --extra_workloads options act only with --full)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; rank 0's pairs)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, time the steps, dump the outputs, print the line
+        args.cpu_pairs = args.cpu_procs = args.e2e_pairs = args.e2e_files = args.extra_workloads = 0
+        args.no_profile = True
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -456,6 +500,7 @@ def extra_workloads(args):
     def leg(name, **kw):
         a = copy.copy(args)
         a.cpu_pairs, a.cpu_procs, a.e2e_pairs, a.e2e_files, a.extra_workloads = 0, 0, 0, 0, 0
+        a.dump_outputs = None
         for k, v in kw.items():
             setattr(a, k, v)
         t = time.perf_counter()
@@ -589,7 +634,9 @@ def bench_ctf(args):
         total_pairs = int(tp.item())
     lib.svx_set_profiling(ctx.h, 0)
     ctx.set_pipeline(False)   # (the legs below -- CPU parity sample, end-to-end, other workloads -- start from the default state)
-    res = None if os.environ.get("SVX_BENCH_NOCHECK") else pb.results()   # (NOCHECK: timing experiments with deliberately wrong kernels)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pb, args.dump_outputs)
+    res = None if os.environ.get("SVX_BENCH_NOCHECK") or not args.full else pb.results()   # (NOCHECK: timing experiments with deliberately wrong kernels)
 
     value = total_pairs / elapsed
     cells = float(np.mean([dp_cells(n, m, W) for n, m in shapes]))

@@ -41,3 +41,28 @@ def pipeline_inputs(c):
     types = alignment_types(c["a"])
     W = c.get("W", int(np.ceil(K / 2.0)) + 5)
     return v0, v1, types, W, dict(dtype=dt)
+
+# tests/test_oracle_vs_reference.py: every intermediate of vecalign() on these seeded cases (N, M, K, d, a, options)
+STACK_CASES = [
+    (40, 37, 3, 64, 4, {}), (237, 217, 5, 64, 6, {}), (700, 650, 4, 64, 5, {}), (1101, 1003, 4, 32, 5, {}),
+    (300, 310, 1, 64, 2, {}), (500, 480, 4, 64, 5, dict(zero_rows=25)), (512, 512, 4, 1024, 5, {}),
+    (420, 400, 3, 64, 4, dict(max_full=50)), (150, 140, 3, 64, 4, dict(max_full=10 ** 6, W=151)),
+]
+STACK_KEYS = ['v0', 'v1', 'n0', 'n1', 'del_penalty', 'costs_1to1', 'x_y_tb', 'alignments', 'searchpath', 'a_b_costs', 'b_offset',
+              'a_b_csum', 'a_b_xp', 'a_b_yp', 'new_b_offset', 'final_alignments', 'alignment_scores']
+
+
+def digest(x, key=None):
+    """sha256 of a value the way the tests compare it, so that recorded results of the reference
+    (tests/golden/reference_records.json) stand in for the values themselves: alignment lists and search paths by
+    their integers, everything else by shape and float64 values (np.array_equal semantics: dtype and -0.0 aside)."""
+    import hashlib
+    import json
+    if key in ('alignments', 'final_alignments'):
+        data = json.dumps([[[int(v) for v in p], [int(v) for v in q]] for p, q in x]).encode()
+    elif key == 'searchpath':
+        data = json.dumps([[int(v) for v in p] for p in x]).encode()
+    else:
+        a = np.asarray(x, dtype=np.float64) + 0.0
+        data = repr(a.shape).encode() + np.ascontiguousarray(a).tobytes()
+    return hashlib.sha256(data).hexdigest()

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import ref_loader  # noqa: E402
 from synth import alignment_types, make_pair, round_bf16  # noqa: E402
-from cases import OPS_CASE, PIPELINE_CASES, EXAMPLE_TRIM, pipeline_inputs  # noqa: E402
+from cases import OPS_CASE, PIPELINE_CASES, EXAMPLE_TRIM, STACK_CASES, digest, pipeline_inputs  # noqa: E402
 
 
 def rows_of(alignments):
@@ -215,13 +215,99 @@ def gen_post(ref_root):
     print("example_post:", sum(os.path.getsize(os.path.join(od, f)) for f in os.listdir(od)) // 1024, "KiB")
 
 
+def gen_example_files(ref_root):
+    """More data files of the shipped example (tests/golden/example_files), copied as they are: the untranslated
+    segment lists and the alignment files of the post-filter chain (align_0.7 ... align_0.7_clean_cat3_min1s)."""
+    import shutil
+    ex = os.path.join(ref_root, "example", "voxpopuli")
+    stem = "20180313-0900-PLENARY-15"
+    name = f"{stem}_en-{stem}_de"
+    od = os.path.join(HERE, "example_files")
+    os.makedirs(od, exist_ok=True)
+    files = [(f"untrans_segs/en-de/{name}.{side}.txt", f"untrans_segs_{side}.txt") for side in ("src", "tgt")]
+    files += [(f"{sub}/en-de/{name}.txt", f"{sub}.txt")
+              for sub in ("align_0.7", "align_0.7_clean", "align_0.7_clean_cat3", "align_0.7_clean_cat3_min1s")]
+    for src, dst in files:
+        shutil.copyfile(os.path.join(ex, src), os.path.join(od, dst))
+        os.chmod(os.path.join(od, dst), 0o644)
+    print("example_files:", sum(os.path.getsize(os.path.join(od, f)) for f in os.listdir(od)) // 1024, "KiB")
+
+
+def gen_records(ref):
+    """tests/golden/reference_records.json: what the reference's own functions return on the shipped example and on
+    seeded synthetic inputs, for the tests that pin the mirror and the oracle against it (recorded results only; large
+    arrays as sha256 digests, see cases.digest())."""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "speech-vecalign_amd"))
+    from svx.vecalign.vecalign import load_ignore_index_file
+    from cases import STACK_KEYS as KEYS
+    rec = {"types": {str(a): [ref.vecalign.make_alignment_types(a), ref.vecalign.make_many_to_one_alignment_types(a)]
+                     for a in range(2, 12)}}
+    # make_doc_embedding on the shipped example (tests/golden/example_full)
+    full = os.path.join(HERE, "example_full")
+    rec["candidate_tensor"] = {}
+    for lang, side in (("en", "src"), ("de", "tgt")):
+        cat = os.path.join(full, f"cat_segs_{lang}.txt")
+        emb = np.fromfile(os.path.join(full, f"embeds_{lang}.f16"), dtype=np.float16).reshape(-1, 1024).astype(np.float32)
+        lines = open(os.path.join(full, f"segments_{lang}.txt")).readlines()
+        r_s2i = {}
+        for i, line in enumerate(open(cat)):
+            r_s2i.setdefault(line.strip(), i)
+        ign = load_ignore_index_file(os.path.join(full, f"ignore_{side}.txt"))
+        theirs = ref.embedding_utils.make_doc_embedding(r_s2i, emb, lines, 5, ignore_indices=ign, overlap_segments=True)
+        rec["candidate_tensor"][lang] = {"shape": list(theirs.shape), "dtype": str(theirs.dtype), "sha256": digest(theirs)}
+    # score_multiple on the shipped alignment files against the gold alignment
+    files = os.path.join(HERE, "example_files")
+    gold = ref.file_utils.read_alignments(os.path.join(full, "gold.txt"))
+    rec["score_multiple"] = {}
+    for sub, path in (("alignments", os.path.join(full, "shipped_alignment.txt")), ("align_0.7", os.path.join(files, "align_0.7.txt"))):
+        rec["score_multiple"][sub] = ref.score.score_multiple(gold_list=[gold], test_list=[ref.file_utils.read_alignments(path)])
+    # every intermediate of dp_utils.vecalign() on the seeded cases of tests/test_oracle_vs_reference.py
+    rec["stack"] = {}
+    for case in STACK_CASES:
+        N, M, K, d, a, kw = case
+        v0, v1 = make_pair(N, M, K, d, 1, zero_rows=kw.get("zero_rows", 0))
+        W = kw.get("W", int(np.ceil((a - 1) / 2.0)) + 5)
+        np.random.seed(3)
+        sr = ref.dp_utils.vecalign(v0.copy(), v1.copy(), ref.vecalign.make_alignment_types(a), 0.2, W, kw.get("max_full", 300), 20000, 100)
+        rec["stack"][repr(case)] = {str(dep): {key: digest(sr[dep][key], key) for key in KEYS if key in sr[dep]} for dep in sorted(sr)}
+    # numpy's global stream as the reference consumes it (np.random.choice calls, in order)
+    calls = []
+    real = np.random.choice
+
+    def spy(a, size=None, replace=True, p=None):
+        out = real(a, size=size, replace=replace, p=p)
+        calls.append(np.asarray(out).astype(np.int32))
+        return out
+    v0, v1 = make_pair(1100, 1000, 4, 32, 2)
+    np.random.seed(9)
+    np.random.choice = spy
+    try:
+        ref.dp_utils.vecalign(v0.copy(), v1.copy(), alignment_types(5), 0.2, 7, 300, 20000, 100)
+    finally:
+        np.random.choice = real
+    flat = np.concatenate(calls)
+    rec["rng_draws"] = {"count": int(flat.size), "sha256": digest(flat)}
+    # the Flat index faiss wrote for the shipped margin example (its rows are margin_example.npz's db_src)
+    import hashlib
+    idx = open(os.path.join(ref.root, "example", "voxpopuli", "align_0.7_clean_cat3_min1s_embed_indexes", "en-de", "en",
+                            "Flat.populate.idx"), "rb").read()
+    rec["flat_index_en"] = {"bytes": len(idx), "sha256": hashlib.sha256(idx).hexdigest()}
+    with open(os.path.join(HERE, "reference_records.json"), "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("reference_records.json:", os.path.getsize(os.path.join(HERE, "reference_records.json")) // 1024, "KiB")
+
+
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["ops", "pipeline", "example", "example_full", "margin", "post"]
+    what = sys.argv[1:] or ["ops", "pipeline", "example", "example_full", "margin", "post", "example_files", "records"]
     if "post" in what:
         gen_post(ref_loader.REF_ROOT)
+    if "example_files" in what:
+        gen_example_files(ref_loader.REF_ROOT)
     if "margin" in what:
         gen_margin(ref_loader.REF_ROOT)
-    if set(what) - {"margin", "post"}:
+    if set(what) - {"margin", "post", "example_files"}:
         ref = ref_loader.load()
         if "ops" in what:
             gen_ops(ref)
@@ -231,3 +317,5 @@ if __name__ == "__main__":
             gen_example(ref)
         if "example_full" in what:
             gen_example_full(ref)
+    if "records" in what:
+        gen_records(ref_loader.load())

@@ -1,18 +1,45 @@
 """Host-side logic of the path (no GPU): alignment types, search parameters, file formats, candidate
 index tables, scoring, sharding, CLI surface.  Where the reference is present (build container) the
-results are compared with the reference's own functions; otherwise with fixtures / known answers."""
+results are compared with what the reference's own functions returned (tests/golden/reference_records.json) or with
+its shipped example files (tests/golden/example_full, example_files); otherwise with known answers."""
+import json
 import os
-import sys
+import shutil
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import ref_loader  # noqa: E402
+from cases import digest
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRIM = os.path.join(ROOT, "tests", "golden", "example_trim")
-needs_ref = pytest.mark.skipif(not ref_loader.available(), reason="reference not present (GPU box)")
+FULL = os.path.join(ROOT, "tests", "golden", "example_full")
+FILES = os.path.join(ROOT, "tests", "golden", "example_files")
+STEM = "20180313-0900-PLENARY-15"
+
+
+def reference_records():
+    with open(os.path.join(ROOT, "tests", "golden", "reference_records.json")) as f:
+        return json.load(f)
+
+
+def shipped_example(root):
+    """The shipped example's directory tree (example/voxpopuli, en-de) rebuilt under `root` from the fixtures."""
+    name = f"{STEM}_en-{STEM}_de"
+    files = {"metadata.tsv": os.path.join(ROOT, "tests", "golden", "example_post", "metadata.tsv"),
+             f"{STEM}.gold": os.path.join(FULL, "gold.txt"),
+             f"alignments/en-de/{name}.txt": os.path.join(FULL, "shipped_alignment.txt")}
+    for lang, side in (("en", "src"), ("de", "tgt")):
+        files[f"segments/{lang}/{STEM}_{lang}.txt"] = os.path.join(FULL, f"segments_{lang}.txt")
+        files[f"cat_segs/{lang}/{STEM}_{lang}.txt"] = os.path.join(FULL, f"cat_segs_{lang}.txt")
+        files[f"untrans_cat_seg_ids/en-de/{name}.{side}.txt"] = os.path.join(FULL, f"ignore_{side}.txt")
+        files[f"untrans_segs/en-de/{name}.{side}.txt"] = os.path.join(FILES, f"untrans_segs_{side}.txt")
+    for sub in ("align_0.7", "align_0.7_clean", "align_0.7_clean_cat3", "align_0.7_clean_cat3_min1s"):
+        files[f"{sub}/en-de/{name}.txt"] = os.path.join(FILES, f"{sub}.txt")
+    for dst, src in files.items():
+        os.makedirs(os.path.dirname(os.path.join(root, dst)), exist_ok=True)
+        shutil.copyfile(src, os.path.join(root, dst))
+    return str(root)
 
 
 def test_alignment_types_and_search_params():
@@ -31,13 +58,12 @@ def test_alignment_types_and_search_params():
     assert (types, sk, tk, W) == ([(1, 1), (2, 1), (3, 1), (4, 1)], 4, 1, 7)
 
 
-@needs_ref
 def test_types_match_reference():
     from svx.vecalign import vecalign as V
-    ref = ref_loader.load()
+    ref = reference_records()["types"]
     for a in range(2, 12):
-        assert V.make_alignment_types(a) == ref.vecalign.make_alignment_types(a)
-        assert V.make_many_to_one_alignment_types(a) == ref.vecalign.make_many_to_one_alignment_types(a)
+        assert V.make_alignment_types(a) == [tuple(t) for t in ref[str(a)][0]]
+        assert V.make_many_to_one_alignment_types(a) == [tuple(t) for t in ref[str(a)][1]]
 
 
 def test_alignment_files_round_trip(tmp_path):
@@ -94,42 +120,32 @@ def test_candidate_index_table_fixture():
         assert got.dtype == np.float16 and np.array_equal(np.asarray(got), np.asarray(emb[:7]))
 
 
-@needs_ref
 def test_candidate_tensor_matches_reference():
     """table + gather == the reference's make_doc_embedding, bit for bit, on the shipped example."""
     from svx.utils import embedding_utils as E
-    ref = ref_loader.load()
-    ex = os.path.join(ref.root, "example", "voxpopuli")
-    stem = "20180313-0900-PLENARY-15"
+    from svx.vecalign.vecalign import load_ignore_index_file
+    ref = reference_records()["candidate_tensor"]
     for lang, side in (("en", "src"), ("de", "tgt")):
-        cat = os.path.join(ex, "cat_segs", lang, f"{stem}_{lang}.txt")
-        s2i, emb = E.read_in_embeddings(cat, os.path.join(ex, "embeds", lang, f"{stem}_{lang}.embed"), use_stopes=True)
-        lines = open(os.path.join(ex, "segments", lang, f"{stem}_{lang}.txt")).readlines()
-        ign = ref.vecalign.load_ignore_index_file(os.path.join(ex, "untrans_cat_seg_ids", "en-de", f"{stem}_en-{stem}_de.{side}.txt"))
+        cat = os.path.join(FULL, f"cat_segs_{lang}.txt")
+        s2i, emb = E.read_in_embeddings(cat, os.path.join(FULL, f"embeds_{lang}.f16"), False, True)
+        lines = open(os.path.join(FULL, f"segments_{lang}.txt")).readlines()
+        ign = load_ignore_index_file(os.path.join(FULL, f"ignore_{side}.txt"))
         tab = E.candidate_index_table(s2i, lines, 5, ign, overlap_segments=True)
         mine = np.where(tab[..., None] >= 0, np.asarray(emb, dtype=np.float32)[np.clip(tab, 0, None)], 0.0).astype(np.float32)
-        r_s2i = {}
-        for i, l in enumerate(open(cat)):
-            r_s2i.setdefault(l.strip(), i)
-        theirs = ref.embedding_utils.make_doc_embedding(r_s2i, np.asarray(emb, dtype=np.float32), lines, 5, ignore_indices=ign,
-                                                        overlap_segments=True)
-        assert np.array_equal(mine, theirs)
+        assert (list(mine.shape), str(mine.dtype)) == (ref[lang]["shape"], ref[lang]["dtype"])
+        assert digest(mine) == ref[lang]["sha256"]
 
 
-@needs_ref
 def test_score_reproduces_readme_tables():
     """README.md:289-295 / 318-325 quality tables from the shipped alignment files."""
     from svx.utils.file_utils import read_alignments
     from svx.vecalign.score import score_multiple
-    ref = ref_loader.load()
-    ex = os.path.join(ref.root, "example", "voxpopuli")
-    stem = "20180313-0900-PLENARY-15"
-    gold = read_alignments(os.path.join(ex, f"{stem}.gold"))
-    name = f"{stem}_en-{stem}_de.txt"
+    ref = reference_records()["score_multiple"]
+    gold = read_alignments(os.path.join(FULL, "gold.txt"))
     for sub, want in (("alignments", (0.558, 0.632, 0.593, 0.942, 0.993, 0.967)), ("align_0.7", (0.593, 0.632, 0.612, 0.972, 0.978, 0.975))):
-        test = read_alignments(os.path.join(ex, sub, "en-de", name))
+        test = read_alignments(os.path.join(FULL, "shipped_alignment.txt") if sub == "alignments" else os.path.join(FILES, sub + ".txt"))
         mine = score_multiple([gold], [test])
-        theirs = ref.score.score_multiple(gold_list=[gold], test_list=[test])
+        theirs = ref[sub]
         assert mine == theirs
         got = (mine["precision_strict"], mine["recall_strict"], mine["f1_strict"], mine["precision_lax"], mine["recall_lax"], mine["f1_lax"])
         assert all(abs(g - w) < 6e-4 for g, w in zip(got, want))
@@ -224,13 +240,11 @@ def test_concat_segs_and_untranslated_fixture(tmp_path):
     assert D.get_identical_overlap_ids(tmp_path / "segs.txt", 3, 320000, tmp_path / "ident.txt") == [(0, 1), (1, 1), (3, 4), (4, 4)]
 
 
-@needs_ref
 def test_concat_segs_and_untranslated_match_shipped_example(tmp_path):
     """Byte-exact regeneration of example/voxpopuli/cat_segs and untrans_cat_seg_ids."""
     from svx.seg_align import concat_segs as C
     from svx.seg_align import detect_untranslate_concats as D
-    ref = ref_loader.load()
-    ex = os.path.join(ref.root, "example", "voxpopuli")
+    ex = shipped_example(tmp_path / "example")
     stem = "20180313-0900-PLENARY-15"
     for lang, side in (("en", "src"), ("de", "tgt")):
         seg = os.path.join(ex, "segments", lang, f"{stem}_{lang}.txt")
@@ -259,12 +273,10 @@ def test_postfilters_known_answers(tmp_path):
     assert (tmp_path / "d.txt").read_text() == "[0]:[0]\n[2]:[2]\n"
 
 
-@needs_ref
 def test_postfilters_regenerate_shipped_example(tmp_path):
     """align_0.7, align_0.7_clean_cat3 and ..._min1s regenerate byte-identically from their predecessors."""
     from svx.postprocess import concat_aligns, filter_by_cost, filter_by_dur
-    ref = ref_loader.load()
-    ex = os.path.join(ref.root, "example", "voxpopuli")
+    ex = shipped_example(tmp_path / "example")
     name = "en-de/20180313-0900-PLENARY-15_en-20180313-0900-PLENARY-15_de.txt"
     common = ["--src_lang", "en", "--tgt_lang", "de"]
     meta = os.path.join(ex, "metadata.tsv")

@@ -16,7 +16,6 @@ import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GD = os.path.join(ROOT, "tests", "golden")
-REF_IDX = "/root/reference/example/voxpopuli/align_0.7_clean_cat3_min1s_embed_indexes/en-de/en/Flat.populate.idx"
 
 
 def unit_rows(n, d, seed, clusters=0):
@@ -73,16 +72,20 @@ def test_faiss_flat_file_roundtrip(tmp_path):
         read_faiss_flat(tmp_path / "short.idx")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_IDX), reason="reference example not present")
 def test_reader_on_the_reference_index_file(tmp_path):
-    """Our writer produces byte-for-byte the file faiss wrote for the reference's example."""
+    """Our writer produces byte-for-byte the file faiss wrote for the reference's example (its size and sha256 are
+    recorded in tests/golden/reference_records.json), and our reader reads that file back to the example's rows."""
+    import hashlib
+    import json
     from svx.postprocess.flat_index import read_faiss_flat, write_faiss_flat
-    rows = read_faiss_flat(REF_IDX)
+    ref = json.load(open(os.path.join(GD, "reference_records.json")))["flat_index_en"]
     g = np.load(os.path.join(GD, "margin_example.npz"))
+    write_faiss_flat(tmp_path / "w.idx", g["db_src"].astype(np.float32))
+    data = (tmp_path / "w.idx").read_bytes()
+    assert (len(data), hashlib.sha256(data).hexdigest()) == (ref["bytes"], ref["sha256"])
+    rows = read_faiss_flat(tmp_path / "w.idx")
     assert np.array_equal(np.asarray(rows), g["db_src"].astype(np.float32))
     assert np.abs(np.linalg.norm(rows, axis=1) - 1).max() < 1e-3
-    write_faiss_flat(tmp_path / "w.idx", np.asarray(rows))
-    assert (tmp_path / "w.idx").read_bytes() == open(REF_IDX, "rb").read()
 
 
 def test_tsv_loader_and_writers(tmp_path):
