@@ -219,7 +219,9 @@ typedef struct svx_align_params {
  * coarse alignment: Sakoe-Chiba search (BASELINE configs[3]), and with width_over2 > max(N, M) every cell of
  * the lattice (what vecalign() evaluates with max_size_full_dp = infinity; SURVEY.md 8a, Modes B / C).  Bands wider
  * than 64 cells run as a wavefront of 32 x 32 tiles over all CUs, the costs of a tile computed on the matrix cores
- * and consumed from LDS (no [T][A][B] cost tensor in memory). */
+ * (no [T][A][B] cost tensor in memory).  Every band width takes the type sets COARSE_TO_FINE takes (<= 128 types,
+ * sizes <= 100): up to 16 types on up to 12 overlap layers with steps <= 8 keep a tile's costs in LDS; larger sets
+ * stream them through a per-CU plane buffer of ceil(T/8)*8 x 4 KB (counted in svx_scratch_bytes). */
 #define SVX_SEARCH_COARSE_TO_FINE 0
 #define SVX_SEARCH_STRAIGHT 1
 

@@ -62,6 +62,7 @@ struct HalfState {
     int max_nblk[SVX_MAX_LEVELS] = {0}, max_A[SVX_MAX_LEVELS] = {0};
     bool any_L0 = false;
     size_t o_tickets = 0;
+    size_t o_planes = 0, b_planes = 0;   // cost planes of the general tile shape (one slice per persistent workgroup)
     // inputs of the launch-order cost model (microseconds are estimated from these; accuracy is not needed)
     double b_pyr[SVX_MAX_LEVELS] = {0}, b_bc[SVX_MAX_LEVELS] = {0}, b_knobN = 0, b_knob0 = 0, dense_cells = 0;
     BatchParams bp;
@@ -563,6 +564,7 @@ static int plan_half(svx_ctx* ctx, HalfState& H, const BatchParams& bp, const sv
     H.maxL = H.max_ksum = H.max_kn = H.max_ds0 = H.max_ds1 = H.max_n0 = H.max_tnd = 0;
     H.any_L0 = false;
     H.o_tickets = 0;
+    H.o_planes = H.b_planes = 0;
     H.b_knobN = H.b_knob0 = H.dense_cells = 0;
     for (int l = 0; l < SVX_MAX_LEVELS; l++) { H.max_nblk[l] = H.max_A[l] = 0; H.b_pyr[l] = H.b_bc[l] = 0; }
     Bump bump;
@@ -708,7 +710,11 @@ static int plan_half(svx_ctx* ctx, HalfState& H, const BatchParams& bp, const sv
 #undef OFF
     for (int p = 0; p < n_pairs; p++)
         if (host[p].t_nd > H.max_tnd) H.max_tnd = host[p].t_nd;
-    if (tiles) H.o_tickets = bump.take(((size_t)(H.max_tnd + 2) * n_pairs + 2) * sizeof(int));
+    if (tiles) {
+        H.o_tickets = bump.take(((size_t)(H.max_tnd + 2) * n_pairs + 2) * sizeof(int));
+        H.b_planes = svxl_band_tiles_scratch(tfinal);  // (independent of the pairs: CUs x types x 4 KB)
+        if (H.b_planes) H.o_planes = bump.take(H.b_planes);
+    }
     // ---- the half's arena (grow-only).  Growing it frees memory that launched work may still use: wait for the device
     // first (rare: arenas settle after the first calls)
     if (bump.off > H.arena_bytes) {
@@ -933,7 +939,8 @@ static void chain_segs(svx_ctx* ctx, HalfState& H, std::vector<Seg>& segs) {
         if (bp.tiles) {
             cur.s = {1.0e4, S_TILES, [=]() {
                 int* tk = reinterpret_cast<int*>(h->arena + h->o_tickets);
-                return svxl_band_tiles_batch(ctx, h->dpairs, np, ty, W, dtype, h->max_tnd, tk, tk + (size_t)h->max_tnd * np + 1);
+                float* planes = h->b_planes ? reinterpret_cast<float*>(h->arena + h->o_planes) : nullptr;
+                return svxl_band_tiles_batch(ctx, h->dpairs, np, ty, W, dtype, h->max_tnd, tk, tk + (size_t)h->max_tnd * np + 1, planes);
             }};
         } else {
             cur.s = {H.b_bc[depth] / 4.0e6, depth == 0 ? S_BAND_COSTS0 : S_BAND_COSTSN, [=]() {
@@ -1102,10 +1109,8 @@ extern "C" int svx_align_batch(svx_ctx* ctx, const svx_align_params* prm, const 
     bp.straight = prm->search_mode == SVX_SEARCH_STRAIGHT;
     // straight search with a band wider than the one-workgroup DP kernel takes: wavefront of tiles (svx_tiles.hip)
     bp.tiles = bp.straight && bp.B > 64;
-    if (bp.tiles) {
-        NEED(ctx, bp.packable && bp.tfinal.n >= 1 && svxl_band_tiles_ok(bp.tfinal),
-             "wide straight band: the tile kernel takes 1..16 alignment types on <= 12 overlap layers with steps <= 8");
-    }
+    // (shape: the two LDS-resident ones for the sets they take, else the general one; every set make_types accepts)
+    if (bp.tiles) NEED(ctx, bp.tfinal.n >= 1 && svxl_band_tiles_shape(bp.tfinal) >= 0, "wide straight band: no tile shape takes these %d alignment types", bp.tfinal.n);
     if ((rc = ensure_streams(ctx))) return rc;
     for (int i = 0; i < S_COUNT; i++) { cx->ms[i] = 0.0; cx->launches[i] = 0; }
     for (auto& r : cx->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }

@@ -287,9 +287,10 @@ bool svxl_band2_limits(const SvxTypes& types, int W, int depth, int dtype, int d
 int svxl_band_costs2_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int depth, int max_A, const SvxTypes& types, int W,
                            int dtype, int d);
 // wide bands as a wavefront of tiles (svx_tiles.hip)
-bool svxl_band_tiles_ok(const SvxTypes& types);
+int svxl_band_tiles_shape(const SvxTypes& types);
+size_t svxl_band_tiles_scratch(const SvxTypes& types);
 int svxl_band_tiles_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, const SvxTypes& types, int W, int dtype, int max_nd,
-                          int* gpref, int* ticket);
+                          int* gpref, int* ticket, float* planes);
 // dp (svx_dp.hip)
 int svxl_dense_dp(svx_ctx*, const float* cost, int s0, int s1, float pen, double* csum, int* bp);
 int svxl_dense_stage_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int max_s0);

@@ -19,7 +19,8 @@
 // ticket has a smaller number, hence is already claimed by a running workgroup: no deadlock under any dispatch
 // order -- compute the cost planes first (they need no neighbour), then wait for the neighbours' flags.
 // Results go to the reference's node arrays (csum [A+2][B] float64, packed back-pointers), which the existing
-// traceback kernel walks.
+// traceback kernel walks.  Type sets beyond these two LDS-resident shapes run k_band_tiles_gen below (planes through
+// a per-workgroup slice of global scratch, halo of the largest step, int32 back-pointers for steps above 15).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -576,6 +577,476 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
     }
 }
 
+// ---- general shape: any type set make_types accepts (<= 128 types, sizes <= 100).
+// The costs phase runs once per GROUP of <= 16 types on <= 12 overlap slots (the medium shape's register and ring budget)
+// and writes the group's planes to this workgroup's own slice of global scratch, laid out [t / 8][x row][y row][t % 8]:
+// the eight move slots of a DP node read 32 contiguous bytes.  The DP phase reads them back one node diagonal ahead.
+// The csum tile is (32 + Hx) x (32 + Hy) with Hx / Hy the largest x / y step (up to 100, beyond the tile side).
+// Back-pointers leave as packed bytes when the steps allow it, else as the int32 xp / yp arrays.
+// LDS: the four ring stages are separate objects, so that the compiler's LDS-DMA tracking lets a ring read wait for its
+// own slab only (one array holding all four makes it wait for every slab in flight: vmcnt(0) in front of each read).
+// Beside the 96 KB ring, the csum tile takes up to TG_CSSMALL doubles: every halo with (32 + Hx)(32 + Hy) within it.
+// Larger halos (both steps large, e.g. (100, 1) and (1, 100) in one set) take the BIGH variant, whose csum tile shares
+// one array with the ring (idle by then) -- and whose ring is serialised by that wait.
+constexpr int TG_MAXG = 32, TG_MAXH = 100;
+constexpr int TG_NSLOT = 12, TG_UPW = 8, TG_S = 4;
+constexpr int TG_CSMAX = (TL + TG_MAXH) * (TL + TG_MAXH) + 1;
+constexpr int TG_CSSMALL = 7040;
+
+struct TileGroup {
+    unsigned char nslot, nt, pad_[2];
+    unsigned char slot_info[TT_MAXSLOT];  // side << 7 | layer
+    unsigned char type_id[TT_MAXT];       // index into the type set
+    unsigned char type_slots[TT_MAXT];    // x slot | y slot << 4
+};
+
+struct TilePlanGen {
+    int ng, hx, hy, nplane;  // groups, largest x / y step, type planes per workgroup slice (T rounded up to 8)
+    TileGroup g[TG_MAXG];
+};
+
+template <typename E, int MS, bool BIGH>
+__global__ __launch_bounds__(TT_THREADS) void k_band_tiles_gen(const SvxPairDev* __restrict__ pairs, int n_pairs, SvxTypes ty, TilePlanGen plan,
+                                                               int W, int max_nd, const int* __restrict__ gpref, int* ticket, float* planes_all,
+                                                               unsigned long long* prof) {
+    using C = TileCfg<E, TG_NSLOT, TG_UPW, TG_S>;
+    using St = typename E::storage;
+    constexpr int PW = C::PW;
+    constexpr int RING = TG_S * C::STAGE;
+    constexpr int LDS_MAIN = (RING > TG_CSMAX * 8 ? RING : TG_CSMAX * 8);
+    constexpr int STG = BIGH ? 16 : C::STAGE;
+    __shared__ __attribute__((aligned(1024))) char st0[STG];
+    __shared__ __attribute__((aligned(1024))) char st1[STG];
+    __shared__ __attribute__((aligned(1024))) char st2[STG];
+    __shared__ __attribute__((aligned(1024))) char st3[STG];
+    __shared__ __attribute__((aligned(16))) double csl[BIGH ? 2 : TG_CSSMALL];
+    __shared__ __attribute__((aligned(1024))) char lmain[BIGH ? LDS_MAIN : 16];  // BIGH: DMA ring, then the csum tile
+    __shared__ unsigned short bpt[TL * TL];                         // x step | y step << 8, 0xFFFF = unreachable
+    __shared__ float snrm[TG_NSLOT * TL], sinv[TG_NSLOT * TL];
+    __shared__ int bo_l[2 * TL + 2 * TG_MAXH + 2];
+    __shared__ int tpk[SVX_MAX_TYPES + 2];
+    __shared__ int sh_ticket;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int B = 2 * W, T = ty.n, NTt = T + 2, HX = plan.hx, HY = plan.hy, CSY = TL + plan.hy;
+    const int NCS = (TL + HX) * CSY;   // cs[NCS] = +inf
+    double* cs = BIGH ? reinterpret_cast<double*>(lmain) : csl;
+    float* pl = planes_all + (size_t)blockIdx.x * plan.nplane * TL * TL;
+    const long long nent = (long long)max_nd * n_pairs;
+    const int total = gpref[nent];
+    for (int t = tid; t < NTt; t += TT_THREADS) tpk[t] = (int)ty.x[t] | ((int)ty.y[t] << 8);
+    const int lrow = lane & 15, lkg = lane >> 4;
+    const int loff = lrow * TT_SLAB + 16 * (lkg ^ swz_t(lrow));
+    const double inf = __builtin_inf();
+    long long ecur = 0;
+
+    unsigned long long t_prev = prof ? __builtin_amdgcn_s_memrealtime() : 0;
+    auto stamp = [&](int slot) {
+        if (prof && tid == 0) {
+            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+            atomicAdd(prof + slot, now - t_prev);
+            t_prev = now;
+        }
+    };
+    for (;;) {
+        __syncthreads();
+        stamp(6);
+        if (tid == 0) sh_ticket = atomicAdd(ticket, 1);
+        __syncthreads();
+        const int tk = sh_ticket;
+        if (tk >= total) break;
+        if (gpref[ecur + 1] <= tk) {
+            long long step = 1, lo = ecur + 1, hi = nent - 1;
+            while (lo + step < nent && gpref[lo + step] <= tk) { lo += step; step <<= 1; }
+            if (lo + step < hi) hi = lo + step;
+            while (lo < hi) {
+                const long long mid = (lo + hi + 1) >> 1;
+                if (gpref[mid] <= tk) lo = mid; else hi = mid - 1;
+            }
+            ecur = lo;
+        }
+        const int s = (int)(ecur / n_pairs);
+        const SvxPairDev& P = pairs[ecur % n_pairs];
+        const SvxLevel& Lv = P.lev[0];
+        const int I = P.t_lo[s] + (tk - gpref[ecur]), J = s - I;
+        const int xs = Lv.n[0], ys = Lv.n[1], d = P.d;
+        const int rowbytes = d * (int)sizeof(St);
+        const int NK = (rowbytes + TT_SLAB - 1) / TT_SLAB;
+        const int X0 = TL * I - 1, Y0 = TL * J - 1;
+        const int A = *Lv.path_len;
+        const double pen = *Lv.pen;
+
+        stamp(0);
+        // ---- phase 1: cost planes, one group of types at a time, into this workgroup's scratch slice
+        char* stages[TG_S] = {BIGH ? lmain : st0, BIGH ? lmain + C::STAGE : st1, BIGH ? lmain + 2 * C::STAGE : st2,
+                              BIGH ? lmain + 3 * C::STAGE : st3};
+        for (int gi_ = 0; gi_ < plan.ng; gi_++) {
+            const TileGroup& G = plan.g[gi_];
+            __syncthreads();  // the previous group is finished with the ring and the row norms
+            constexpr int SPT = (TG_NSLOT * TL + TT_THREADS - 1) / TT_THREADS;
+#pragma unroll
+            for (int i = 0; i < SPT; i++) {
+                const int r = tid + i * TT_THREADS;
+                if (r < TG_NSLOT * TL) {
+                    float nv = 0.f, iv = 1.f;
+                    const int slot = r / TL, loc = r % TL;
+                    if (slot < G.nslot) {
+                        const int side = G.slot_info[slot] >> 7, layer = G.slot_info[slot] & 127;
+                        const int gi = (side ? Y0 : X0) + loc, nn = side ? ys : xs;
+                        if (gi >= 0 && gi < nn) {
+                            const size_t o = (size_t)layer * nn + gi;
+                            nv = Lv.nrm[side][o];
+                            if (Lv.inv[side]) iv = Lv.inv[side][o];
+                        }
+                    }
+                    snrm[r] = nv;
+                    sinv[r] = iv;
+                }
+            }
+            const char* src[PW];
+            unsigned live = 0;
+#pragma unroll
+            for (int i = 0; i < PW; i++) {
+                const int q = wave + TT_WAVES * i;
+                const int r = 16 * q + (lane >> 2);
+                const int slot = r / TL, loc = r % TL;
+                const int piece = (lane & 3) ^ swz_t(lane >> 2);
+                src[i] = reinterpret_cast<const char*>(tile_zero16);
+                if (slot < G.nslot) {
+                    const int side = G.slot_info[slot] >> 7, layer = G.slot_info[slot] & 127;
+                    const int gi = (side ? Y0 : X0) + loc, nn = side ? ys : xs;
+                    if (gi >= 0 && gi < nn) {
+                        src[i] = reinterpret_cast<const char*>(P.v[side]) + ((size_t)layer * nn + gi) * rowbytes + piece * 16;
+                        live |= 1u << i;
+                    }
+                }
+            }
+            const int piece_byte = ((lane & 3) ^ swz_t(lane >> 2)) * 16;
+            auto issue = [&](int k, char* stage) {
+#pragma unroll
+                for (int i = 0; i < PW; i++) {
+                    const char* s2 = src[i] + (size_t)k * TT_SLAB;
+                    if (!((live >> i) & 1u) || k * TT_SLAB + piece_byte >= rowbytes) s2 = reinterpret_cast<const char*>(tile_zero16);
+                    __builtin_amdgcn_global_load_lds((gptr_t)s2, (lptr_t)(stage + (wave + TT_WAVES * i) * 1024), 16, 0, 0);
+                }
+            };
+            f32x4_t acc[TG_UPW][2];
+            int aoff[TG_UPW], boffb[TG_UPW];
+            const int nunits = G.nt * 2;
+#pragma unroll
+            for (int u2 = 0; u2 < TG_UPW; u2++) {
+                acc[u2][0] = acc[u2][1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+                const int u = wave + TT_WAVES * u2;
+                const int tl = u < nunits ? u / 2 : 0, xt = u % 2;
+                const int tsl = G.type_slots[tl];
+                aoff[u2] = ((tsl & 15) * TL + xt * 16) * TT_SLAB + loff;
+                boffb[u2] = ((tsl >> 4) * TL) * TT_SLAB + loff;
+            }
+            auto mma = [&](const char* stage) {
+                uint4 fa[TG_UPW], fb[TG_UPW][2];
+#pragma unroll
+                for (int u2 = 0; u2 < TG_UPW; u2++)
+                    if (wave + TT_WAVES * u2 < nunits) {
+                        fa[u2] = *reinterpret_cast<const uint4*>(stage + aoff[u2]);
+                        fb[u2][0] = *reinterpret_cast<const uint4*>(stage + boffb[u2]);
+                        fb[u2][1] = *reinterpret_cast<const uint4*>(stage + boffb[u2] + 16 * TT_SLAB);
+                    }
+#pragma unroll
+                for (int u2 = 0; u2 < TG_UPW; u2++)
+                    if (wave + TT_WAVES * u2 < nunits) {
+                        mma_t16<E>(acc[u2][0], fa[u2], fb[u2][0]);
+                        mma_t16<E>(acc[u2][1], fa[u2], fb[u2][1]);
+                    }
+            };
+            static_assert(3 * PW <= 63, "vmcnt range");
+#pragma unroll
+            for (int k = 0; k < TG_S - 1; k++)
+                if (k < NK) issue(k, stages[k]);
+            auto step = [&](int k, const char* rd, char* wr) {
+                if (k < NK) {
+                    const int younger = (NK - 1 - k) < (TG_S - 2) ? (NK - 1 - k) : (TG_S - 2);
+                    if (younger >= 2) wait_vm_t<2 * PW>();
+                    else if (younger == 1) wait_vm_t<PW>();
+                    else wait_vm_t<0>();
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+                    if (k + TG_S - 1 < NK) issue(k + TG_S - 1, wr);
+                    mma(rd);
+                }
+            };
+            for (int k0 = 0; k0 < NK; k0 += TG_S) {
+                step(k0, stages[0], stages[3]);
+                step(k0 + 1, stages[1], stages[0]);
+                step(k0 + 2, stages[2], stages[1]);
+                step(k0 + 3, stages[3], stages[2]);
+            }
+#pragma unroll
+            for (int u2 = 0; u2 < TG_UPW; u2++) {
+                const int u = wave + TT_WAVES * u2;
+                if (u >= nunits) continue;
+                const int tl = u / 2, xt = u % 2;
+                const int t = G.type_id[tl];
+                const int p = tpk[t] & 255, q = tpk[t] >> 8;
+                const int xsl = (G.type_slots[tl] & 15) * TL, ysl = (G.type_slots[tl] >> 4) * TL;
+                float* plt = pl + (size_t)(t >> 3) * (TL * TL * 8) + (t & 7);
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const int yloc = 16 * j + lrow;
+                    const float ny = snrm[ysl + yloc], iy = sinv[ysl + yloc];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int xloc = 16 * xt + 4 * lkg + r;
+                        const float sumx = acc[u2][j][r] * sinv[xsl + xloc] * iy;
+                        plt[(xloc * TL + yloc) * 8] = cost_formula_t(sumx, p, q, snrm[xsl + xloc], ny);
+                    }
+                }
+            }
+        }
+        const int abase = TL * s - HX - HY;
+        for (int i = tid; i < 2 * TL + HX + HY; i += TT_THREADS) {
+            const int a = abase + i;
+            bo_l[i] = (a >= 0 && a < A + 2) ? Lv.boff_out[a] : (1 << 28);
+        }
+        __syncthreads();  // (also: the planes are written, and the ring is free for the csum tile)
+        stamp(1);
+        // ---- phase 2: wait for every band tile that holds halo nodes: rows I - ceil(Hx / 32) .. I, columns
+        // J - ceil(Hy / 32) .. J (all on earlier tile anti-diagonals: smaller tickets, running workgroups)
+        {
+            const int ri = (HX + TL - 1) / TL, rj = (HY + TL - 1) / TL;
+            const int nnb = (ri + 1) * (rj + 1) - 1;
+            for (int e = tid; e < nnb; e += TT_THREADS) {
+                const int ni = I - ri + e / (rj + 1), nj = J - rj + e % (rj + 1), ns = ni + nj;
+                if (ni < 0 || nj < 0) continue;
+                const int off = ni - P.t_lo[ns];
+                if (off < 0 || off >= P.t_cnt[ns]) continue;
+                const int* flag = P.t_flag + P.t_pref[ns] + off;
+                long spins = 0;
+                while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 && spins < (1l << 25)) {
+                    __builtin_amdgcn_s_sleep(2);
+                    spins++;
+                }
+                if (spins >= (1l << 25)) *P.status = SVX_ERR_HIP;
+            }
+        }
+        __syncthreads();
+        stamp(2);
+        // csum tile: position (i + Hx, j + Hy) <-> node (32 I + i, 32 J + j), i in [-Hx, 32), j in [-Hy, 32)
+        for (int e = tid; e <= NCS; e += TT_THREADS) cs[e] = inf;
+        __syncthreads();
+        {
+            const int ntop = HX * CSY, nhalo = ntop + TL * HY;
+            for (int h0 = 0; h0 < nhalo; h0 += 4 * TT_THREADS) {
+                unsigned long long hv[4];
+                int hp[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int h = h0 + tid + u * TT_THREADS;
+                    hp[u] = -1;
+                    hv[u] = 0;
+                    if (h < nhalo) {
+                        int ii, jj;
+                        if (h < ntop) { ii = h / CSY - HX; jj = h % CSY - HY; }
+                        else { ii = (h - ntop) / HY; jj = (h - ntop) % HY - HY; }
+                        const int xx = TL * I + ii, yy = TL * J + jj;
+                        if (xx >= 0 && yy >= 0 && xx <= xs && yy <= ys) {
+                            const int a = xx + yy, b = yy - bo_l[a - abase];
+                            if (b >= 0 && b < B) {
+                                // (sc1 stores drained before the neighbour's flag; sc1 loads behind the flag poll)
+                                hp[u] = (ii + HX) * CSY + (jj + HY);
+                                hv[u] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(Lv.csum) + ((size_t)a * B + b),
+                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (hp[u] >= 0) cs[hp[u]] = __longlong_as_double((long long)hv[u]);
+            }
+        }
+        __syncthreads();
+        stamp(3);
+        // ---- phase 3: the tile's 63 node anti-diagonals; thread = (node column j, move slot), MS moves per slot in
+        // registers, merged by (total, move index) over the node's eight lanes as in k_band_tiles.  The costs of
+        // diagonal dd + 1 are loaded while diagonal dd is relaxed.
+        {
+            const int j = tid >> 3, slot = tid & 7;
+            int m_off[MS], m_key[MS], m_pl[MS];
+            bool use_cv[MS];
+            double cconst[MS];
+#pragma unroll
+            for (int m = 0; m < MS; m++) {
+                const int t = slot + 8 * m;
+                const bool ok = t < NTt;
+                const int pk = ok ? tpk[t] : 0;
+                m_off[m] = ok ? -((pk & 255) * CSY + (pk >> 8)) : 0;
+                m_key[m] = (t << 16) | pk;
+                use_cv[m] = t < T;
+                cconst[m] = ok ? pen : inf;
+                m_pl[m] = (t < T ? m : 0) * (TL * TL * 8) + slot;  // (moves without a plane read any plane of the slice)
+            }
+            const int yy = TL * J + j;
+            const bool y_in = yy <= ys, y_pos = yy >= 1;
+            const int xrel_max = xs - TL * I;
+            const int a0 = TL * (I + J);
+            const int bo_mine = bo_l[a0 + (tid & 63) - abase];
+            const bool edge_tile = I == 0 || J == 0;
+            float cv[MS];
+            auto load_cv = [&](int dd, float* out) {
+                const int i = dd - j;
+                const int ic = (unsigned)i < (unsigned)TL ? i : 0;
+                const float* base = pl + (ic * TL + j) * 8;
+#pragma unroll
+                for (int m = 0; m < MS; m++) out[m] = base[m_pl[m]];
+            };
+            load_cv(0, cv);
+            for (int dd = 0; dd <= 2 * (TL - 1); dd++) {
+                const int i = dd - j;
+                const bool inside = (unsigned)i < (unsigned)TL;
+                const int ic = inside ? i : 0;
+                const int cpos = (ic + HX) * CSY + (j + HY), ppos = ic * TL + j;
+                double pv[MS];
+                float cn[MS];
+                load_cv(dd < 2 * (TL - 1) ? dd + 1 : dd, cn);
+#pragma unroll
+                for (int m = 0; m < MS; m++) pv[m] = cs[cpos + m_off[m]];
+                const int bo = __builtin_amdgcn_readlane(bo_mine, dd);
+                const int b = yy - bo;
+                const bool node = inside & (ic <= xrel_max) & y_in & ((unsigned)b < (unsigned)B);
+                const bool general = node & (TL * I + ic >= 1) & y_pos & (a0 + dd - 2 < A);
+                DpMerge best{pv[0] + (use_cv[0] ? (double)cv[0] : cconst[0]), m_key[0]};
+#pragma unroll
+                for (int m = 1; m < MS; m++) {
+                    const double tot = pv[m] + (use_cv[m] ? (double)cv[m] : cconst[m]);
+                    const bool take = tot < best.tot;
+                    best.tot = take ? tot : best.tot;
+                    best.key = take ? m_key[m] : best.key;
+                }
+#define TILE_MERGE(CTRL)                                                                                                      \
+    {                                                                                                                         \
+        const unsigned long long u_ = __double_as_longlong(best.tot);                                                         \
+        const unsigned lo_ = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u_, CTRL, 0xf, 0xf, true);                      \
+        const unsigned hi_ = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u_ >> 32), CTRL, 0xf, 0xf, true);              \
+        const int ok_ = __builtin_amdgcn_mov_dpp(best.key, CTRL, 0xf, 0xf, true);                                             \
+        const double ot_ = __longlong_as_double(((unsigned long long)hi_ << 32) | lo_);                                       \
+        const bool tk_ = (ot_ < best.tot) | ((ot_ == best.tot) & (ok_ < best.key));                                           \
+        best.tot = tk_ ? ot_ : best.tot;                                                                                      \
+        best.key = tk_ ? ok_ : best.key;                                                                                      \
+    }
+                TILE_MERGE(0xB1)
+                TILE_MERGE(0x4E)
+                TILE_MERGE(0x141)
+#undef TILE_MERGE
+                const bool won = general & (best.tot < inf);
+                double v = won ? best.tot : inf;
+                int bpv = won ? (best.key & 0xFFFF) : 0xFFFF;
+                if (edge_tile) {
+                    const int xx = TL * I + ic;
+                    if (node && xx == 0) { v = pen * (double)yy; bpv = 0 | (1 << 8); }
+                    else if (node && yy == 0) { v = pen * (double)xx; bpv = 1 | (0 << 8); }
+                }
+                if (inside && slot == 0) {
+                    cs[cpos] = node ? v : inf;
+                    bpt[ppos] = (unsigned short)(node ? bpv : 0xFFFF);
+                }
+#pragma unroll
+                for (int m = 0; m < MS; m++) cv[m] = cn[m];
+                // the diagonal is complete before any wave reads it (LDS only: the next diagonal's cost loads stay in flight)
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+            }
+        }
+        __syncthreads();
+        stamp(4);
+        // ---- phase 4: what later tiles read (the last Hx rows and the last Hy columns; all of the tile once a step
+        // reaches 32) sc1 and drained, then the flag; the interior follows with plain stores
+        auto store_nodes = [&](bool edge) {
+            for (int e = tid; e < TL * TL; e += TT_THREADS) {
+                const int i = e / TL, j2 = e % TL;
+                if ((i >= TL - HX || j2 >= TL - HY) != edge) continue;
+                const int xx = TL * I + i, yy = TL * J + j2;
+                if (xx > xs || yy > ys) continue;
+                const int a = xx + yy, b = yy - bo_l[a - abase];
+                if (b < 0 || b >= B) continue;
+                const size_t o = (size_t)a * B + b;
+                const double v = cs[(i + HX) * CSY + (j2 + HY)];
+                if (edge) __hip_atomic_store(reinterpret_cast<unsigned long long*>(Lv.csum) + o, (unsigned long long)__double_as_longlong(v),
+                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else Lv.csum[o] = v;
+                const int bv = bpt[e];
+                if (Lv.bpk) {
+                    Lv.bpk[o] = bv == 0xFFFF ? (unsigned char)0xFF : (unsigned char)(((bv & 255) << 4) | (bv >> 8));
+                } else {
+                    Lv.xp[o] = bv == 0xFFFF ? -42 : (bv & 255);
+                    Lv.yp[o] = bv == 0xFFFF ? -42 : (bv >> 8);
+                }
+            }
+        };
+        store_nodes(true);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) __hip_atomic_store(P.t_flag + P.t_pref[s] + (I - P.t_lo[s]), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        stamp(5);
+        store_nodes(false);
+    }
+}
+
+// Groups of <= 16 types on <= 12 overlap slots for k_band_tiles_gen.  Types are taken in blocks of 4 x 4 sizes (then by
+// size), and a group is closed when the next type would need a 17th type or a 13th slot: neighbouring sizes share their
+// layers.  restream = slots streamed per tile over distinct slots.
+bool make_tile_plan_gen(const SvxTypes& ty, TilePlanGen* plan, double* restream) {
+    memset(plan, 0, sizeof(*plan));
+    const int T = ty.n;
+    if (T < 1 || T > SVX_MAX_TYPES) return false;
+    int order[SVX_MAX_TYPES];
+    for (int t = 0; t < T; t++) order[t] = t;
+    auto key = [&](int t) {
+        const int x = ty.x[t] - 1, y = ty.y[t] - 1;
+        return (((x / 4) * 32 + y / 4) * 128 + x) * 128 + y;
+    };
+    for (int a = 1; a < T; a++)  // (insertion sort: stable, at most 128 entries)
+        for (int b = a; b > 0 && key(order[b]) < key(order[b - 1]); b--) { const int tmp = order[b]; order[b] = order[b - 1]; order[b - 1] = tmp; }
+    bool seen[2][128];
+    memset(seen, 0, sizeof(seen));
+    int distinct = 0, streamed = 0;
+    TileGroup* G = nullptr;
+    int gslot[2][128];
+    for (int k = 0; k < T; k++) {
+        const int t = order[k], lx = ty.x[t] - 1, ly = ty.y[t] - 1;
+        if (lx >= 127 || ly >= 127) return false;
+        if (G) {
+            const int need = (gslot[0][lx] < 0) + (gslot[1][ly] < 0);
+            if (G->nt >= TT_MAXT || G->nslot + need > TG_NSLOT) G = nullptr;
+        }
+        if (!G) {
+            if (plan->ng >= TG_MAXG) return false;
+            G = &plan->g[plan->ng++];
+            for (int s2 = 0; s2 < 2; s2++) for (int l = 0; l < 128; l++) gslot[s2][l] = -1;
+        }
+        const int lay[2] = {lx, ly};
+        for (int s2 = 0; s2 < 2; s2++) {
+            if (gslot[s2][lay[s2]] < 0) {
+                gslot[s2][lay[s2]] = G->nslot;
+                G->slot_info[G->nslot++] = (unsigned char)((s2 << 7) | lay[s2]);
+                streamed++;
+            }
+            if (!seen[s2][lay[s2]]) { seen[s2][lay[s2]] = true; distinct++; }
+        }
+        G->type_id[G->nt] = (unsigned char)t;
+        G->type_slots[G->nt] = (unsigned char)(gslot[0][lx] | (gslot[1][ly] << 4));
+        G->nt++;
+        if (ty.x[t] > plan->hx) plan->hx = ty.x[t];
+        if (ty.y[t] > plan->hy) plan->hy = ty.y[t];
+    }
+    if (plan->hx < 1) plan->hx = 1;  // (the deletions step by one)
+    if (plan->hy < 1) plan->hy = 1;
+    if (plan->hx > TG_MAXH || plan->hy > TG_MAXH) return false;
+    plan->nplane = (T + 7) / 8 * 8;
+    if (restream) *restream = distinct ? (double)streamed / distinct : 1.0;
+    return true;
+}
+
 bool make_tile_plan(const SvxTypes& ty, int tpp, int nslot_max, TilePlan* plan) {
     memset(plan, 0, sizeof(*plan));
     if (ty.n < 1 || ty.n > tpp) return false;
@@ -600,28 +1071,51 @@ bool make_tile_plan(const SvxTypes& ty, int tpp, int nslot_max, TilePlan* plan) 
 
 }  // namespace
 
-// Can the tile kernel take this type set?  (<= 16 types on <= 12 overlap layers, steps of at most 8 segments.)
-bool svxl_band_tiles_ok(const SvxTypes& types) {
+// Which tile shape takes this type set: 0 = <= 10 types on <= 8 layers, 1 = <= 16 types on <= 12 layers (both with
+// steps of at most 8 segments), 2 = the general shape (any set make_types accepts), -1 = none.
+int svxl_band_tiles_shape(const SvxTypes& types) {
     TilePlan plan;
-    return make_tile_plan(types, 10, 8, &plan) || make_tile_plan(types, 16, 12, &plan);
+    if (make_tile_plan(types, 10, 8, &plan)) return 0;
+    if (make_tile_plan(types, 16, 12, &plan)) return 1;
+    TilePlanGen gp;
+    return make_tile_plan_gen(types, &gp, nullptr) ? 2 : -1;
+}
+
+static int tile_cu_count() {
+    int dev = 0, ncu = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    return ncu;
+}
+
+// Global scratch of the general shape: one slice of cost planes per persistent workgroup (T rounded up to 8 planes of
+// 32 x 32 fp32).  0 for the two LDS-resident shapes.
+size_t svxl_band_tiles_scratch(const SvxTypes& types) {
+    TilePlanGen gp;
+    if (svxl_band_tiles_shape(types) != 2 || !make_tile_plan_gen(types, &gp, nullptr)) return 0;
+    return (size_t)tile_cu_count() * gp.nplane * TL * TL * sizeof(float);
 }
 
 // b_offset_out, tile ranges (which also clear the pairs' tile flags), ticket table, then the persistent tile sweep.
 // gpref [max_nd * n_pairs + 1] and ticket live in the arena.
 int svxl_band_tiles_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, const SvxTypes& types, int W, int dtype, int max_nd,
-                          int* gpref, int* ticket) {
+                          int* gpref, int* ticket, float* planes) {
     if (n_pairs <= 0) return SVX_OK;
     hipStream_t st = ctx->stream;
+    const int shape = svxl_band_tiles_shape(types);
+    if (shape < 0)
+        return svx_fail(ctx, SVX_ERR_ARG, "wide band: %d alignment types: no tile shape takes this set", types.n);
     TilePlan plan;
-    const bool small = make_tile_plan(types, 10, 8, &plan);
-    if (!small && !make_tile_plan(types, 16, 12, &plan))
-        return svx_fail(ctx, SVX_ERR_ARG, "wide band: %d alignment types / their overlap layers exceed the tile kernel (16 types, 12 layers, steps <= 8)", types.n);
+    TilePlanGen gplan;
+    double restream = 1.0;
+    if (shape < 2) make_tile_plan(types, shape == 0 ? 10 : 16, shape == 0 ? 8 : 12, &plan);
+    else make_tile_plan_gen(types, &gplan, &restream);
+    const bool bigh = shape == 2 && (TL + gplan.hx) * (TL + gplan.hy) + 1 > TG_CSSMALL;  // csum tile beside the ring or not
+    if (shape == 2 && !planes) return svx_fail(ctx, SVX_ERR_ARG, "wide band: the general tile shape needs its plane scratch");
     hipLaunchKernelGGL(k_tile_ranges, dim3(n_pairs), dim3(256), 0, st, pairs, W, 2 * W);
     hipLaunchKernelGGL(k_tile_prefix, dim3(1), dim3(1024), 0, st, pairs, n_pairs, max_nd, gpref, ticket);
     SVX_LAUNCH_CHECK(ctx, "k_tile_ranges");
-    int dev = 0, ncu = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int ncu = tile_cu_count();  // (the general shape's plane scratch is sized by the same count)
     // one persistent workgroup per CU (> 100 KB of LDS each): all of them are resident, so a workgroup that waits for
     // a neighbour's flag always waits for a running workgroup
     dim3 grid((unsigned)ncu);
@@ -631,15 +1125,30 @@ int svxl_band_tiles_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, co
         SVX_HIP(ctx, hipMalloc(&prof, 8 * sizeof(unsigned long long)));
         SVX_HIP(ctx, hipMemsetAsync(prof, 0, 8 * sizeof(unsigned long long), st));
     }
+    // general shape: moves per DP slot MS = ceil((T + 2) / 8), rounded up to an instantiated count
+    const int ms_need = (types.n + 2 + 7) / 8;
+    static const int ms_set[] = {2, 3, 4, 6, 9, 17};
+    int ms = 17;
+    for (int v : ms_set)
+        if (v >= ms_need) { ms = v; break; }
+#define GEN(E, M, BH) hipLaunchKernelGGL((k_band_tiles_gen<E, M, BH>), grid, dim3(TT_THREADS), 0, st, pairs, n_pairs, types, gplan, W, max_nd, gpref, ticket, planes, prof)
 #define TILES(E)                                                                                                                   \
     do {                                                                                                                           \
-        if (small) hipLaunchKernelGGL((k_band_tiles<E, 8, 5, 5>), grid, dim3(TT_THREADS), 0, st, pairs, n_pairs, types, plan, W, max_nd, gpref, ticket, prof); \
-        else hipLaunchKernelGGL((k_band_tiles<E, 12, 8, 2>), grid, dim3(TT_THREADS), 0, st, pairs, n_pairs, types, plan, W, max_nd, gpref, ticket, prof); \
+        if (shape == 0) hipLaunchKernelGGL((k_band_tiles<E, 8, 5, 5>), grid, dim3(TT_THREADS), 0, st, pairs, n_pairs, types, plan, W, max_nd, gpref, ticket, prof); \
+        else if (shape == 1) hipLaunchKernelGGL((k_band_tiles<E, 12, 8, 2>), grid, dim3(TT_THREADS), 0, st, pairs, n_pairs, types, plan, W, max_nd, gpref, ticket, prof); \
+        else if (bigh) GEN(E, 17, true);   /* (rare: both steps large; one instantiation for every type count) */                 \
+        else if (ms == 2) GEN(E, 2, false);                                                                                        \
+        else if (ms == 3) GEN(E, 3, false);                                                                                        \
+        else if (ms == 4) GEN(E, 4, false);                                                                                        \
+        else if (ms == 6) GEN(E, 6, false);                                                                                        \
+        else if (ms == 9) GEN(E, 9, false);                                                                                        \
+        else GEN(E, 17, false);                                                                                                    \
     } while (0)
     if (dtype == SVX_F32) TILES(ElemF32);
     else if (dtype == SVX_F16) TILES(ElemF16);
     else TILES(ElemBF16);
 #undef TILES
+#undef GEN
     SVX_LAUNCH_CHECK(ctx, "k_band_tiles");
     if (prof) {
         unsigned long long h[8];
@@ -650,6 +1159,12 @@ int svxl_band_tiles_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, co
         // (slot 3 = halo fill, slot 4 = the DP sweep; names follow the stamps' positions)
         fprintf(stderr, "[svx tile sweep, summed over %d workgroups, ms]", ncu);
         for (int i = 0; i < 7; i++) fprintf(stderr, " p%d(%s)=%.2f", i, nm[i], (double)h[i] * 1e-5);
+        if (shape == 2) {
+            int streamed = 0;
+            for (int g = 0; g < gplan.ng; g++) streamed += gplan.g[g].nslot;
+            fprintf(stderr, " | general shape: %d types in %d groups, %d slot-rows streamed per tile, re-stream x%.2f, halo %d x %d%s",
+                    types.n, gplan.ng, streamed, restream, gplan.hx, gplan.hy, bigh ? " (csum tile shares the ring's LDS)" : "");
+        }
         fprintf(stderr, "\n");
     }
     return SVX_OK;
