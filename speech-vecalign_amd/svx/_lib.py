@@ -180,9 +180,10 @@ class Context:
     def set_pipeline(self, on):
         """Software pipeline over consecutive svx_align_batch calls (include/svx.h: svx_set_pipeline); while it is on,
         outputs are complete only after flush() / sync()."""
+        if self._held:   # svx_set_pipeline flushes only on a change of state: the held batches may still have a queued second half
+            self.flush()
         self.check(self.lib.svx_set_pipeline(self.h, 1 if on else 0))
         self.pipeline = bool(on)
-        del self._held[:]   # (switching flushes)
 
     def flush(self):
         self.check(self.lib.svx_flush(self.h))

@@ -269,8 +269,10 @@ class PreparedBatch:
         """Launch the whole pipeline for the batch (asynchronous on the current torch stream)."""
         ctx = self.ctx
         ctx.use_current_stream()
-        ctx.check(ctx.lib.svx_align_batch(ctx.h, ctypes.byref(self.prm), self.cpairs, len(self.vecs)))
-        ctx.hold(self)
+        try:
+            ctx.check(ctx.lib.svx_align_batch(ctx.h, ctypes.byref(self.prm), self.cpairs, len(self.vecs)))
+        finally:   # a call that fails half way may already have queued work that reads this batch
+            ctx.hold(self)
 
     def flush(self):
         """With the context's pipeline on (Context.set_pipeline): launch what run() held back and order it in front of

@@ -63,49 +63,92 @@ def knife_edge(oracle, gpu_pens, ref_pens, gpu_scores_of, ref_scores_of, frac):
     return True, "; ".join(notes)
 
 
-def run_sweep(cases, seed, batch=8, verbose=True, max_size=900):
-    """-> (mismatches, exact ties, penalty knife-edges)"""
-    class A:
-        pass
-    a = A()
-    a.cases, a.seed, a.batch = cases, seed, batch
+DIMS, STRAIGHT_DIMS, STORES = (32, 64, 256), (32, 64, 96, 256), ("f32", "bf16", "f16")
+
+
+def store_round(v, store):
+    from synth import round_bf16
+    if store == "bf16":
+        return round_bf16(v)
+    if store == "f16":
+        return v.astype(np.float16).astype(np.float32)
+    return v
+
+
+def to_devs(hosts, store):
     import torch
-    import oracle
-    from synth import alignment_types, make_pair, round_bf16
-    from svx.vecalign import dp_utils
-    rs = np.random.RandomState(a.seed)
-    t0 = time.time()
-    done = bad = ties = edges = 0
-    while done < a.cases:
-        # one configuration per batch (types / W / thresholds are batch-wide parameters), sizes vary inside it
+    cast = {"bf16": lambda t: t.bfloat16(), "f16": lambda t: t.half(), "f32": lambda t: t}[str(store)]
+    return [(cast(torch.from_numpy(a).cuda()), cast(torch.from_numpy(b).cuda())) for a, b in hosts]
+
+
+def draw_batches(cases, seed, batch=8, max_size=900, dims=DIMS, stores=STORES, zero_rows=3, k4_weight=0.0):
+    """The sweep's cases, one configuration per batch (types / W / thresholds are batch-wide parameters), sizes vary
+    inside it.  Yields (config dict, [(v0, v1) storage-rounded float32], [per-pair RandomState seeds]).  The defaults
+    consume the RandomState exactly as the sweep always did (test_randomised_sweep_small: 160 cases, seed 11).
+    zero_rows: most zero rows per document; k4_weight: share of batches forced to K = 4 / -a 5 (the benchmark's)."""
+    from synth import alignment_types, make_pair
+    rs = np.random.RandomState(seed)
+    done = 0
+    while done < cases:
         K = int(rs.randint(1, 6))
         amax = int(rs.randint(2, K + 2))
+        if k4_weight and rs.rand() < k4_weight:
+            K, amax = 4, 5
         types = alignment_types(amax)
         W = int(rs.randint(3, 12))
         max_full = int(rs.choice([40, 100, 300]))
         sample = int(rs.choice([500, 5000, 20000]))
         nsamp = int(rs.choice([0, 7, 100]))
         frac = float(rs.choice([0.05, 0.2, 0.5]))
-        d = int(rs.choice([32, 64, 256]))
-        store = rs.choice(["f32", "bf16", "f16"])
-        nb = min(a.batch, a.cases - done)
-        hosts, devs = [], []
+        d = int(rs.choice(list(dims)))
+        store = rs.choice(list(stores))
+        nb = min(batch, cases - done)
+        hosts = []
         for i in range(nb):
             n, m = int(rs.randint(1, max_size)), int(rs.randint(1, max_size))
             if rs.rand() < 0.15:
                 n, m = int(rs.randint(1, 12)), int(rs.randint(1, 12))
             v0, v1 = make_pair(n, m, K, d, int(rs.randint(1 << 30)), deletions=int(rs.randint(0, 6)) if min(n, m) > 12 else 0,
-                               zero_rows=int(rs.randint(0, 4)))
-            if store == "bf16":
-                v0, v1 = round_bf16(v0), round_bf16(v1)
-                devs.append((torch.from_numpy(v0).cuda().bfloat16(), torch.from_numpy(v1).cuda().bfloat16()))
-            elif store == "f16":
-                v0, v1 = v0.astype(np.float16).astype(np.float32), v1.astype(np.float16).astype(np.float32)
-                devs.append((torch.from_numpy(v0).cuda().half(), torch.from_numpy(v1).cuda().half()))
-            else:
-                devs.append((torch.from_numpy(v0).cuda(), torch.from_numpy(v1).cuda()))
-            hosts.append((v0, v1))
+                               zero_rows=int(rs.randint(0, zero_rows + 1)))
+            hosts.append((store_round(v0, store), store_round(v1, store)))
         seeds = [int(rs.randint(1 << 30)) for _ in range(nb)]
+        yield dict(K=K, amax=amax, types=types, W=W, max_full=max_full, sample=sample, nsamp=nsamp, frac=frac, d=d, store=str(store)), hosts, seeds
+        done += nb
+
+
+def _oracle_job(args):
+    """One oracle.vecalign call in a worker process (never touches the GPU); only what the sweep reads comes back."""
+    import oracle
+    v0, v1, types, frac, W, max_full, sample, nsamp, seed = args
+    try:
+        ref = oracle.vecalign(v0, v1, types, frac, W, max_full, sample, nsamp, rng=np.random.RandomState(seed))
+    except Exception as e:
+        return e
+    return {dd: {k: ref[dd][k] for k in ('final_alignments', 'alignment_scores', 'del_penalty', 'knob_scores') if k in ref[dd]}
+            for dd in ref}
+
+
+def oracle_pool(workers):
+    """Pool for the oracle side of a sweep (spawn: the workers must not inherit an initialised HIP runtime)."""
+    import multiprocessing
+    return multiprocessing.get_context("spawn").Pool(min(int(workers), 16)) if workers else None
+
+
+def run_sweep(cases, seed, batch=8, verbose=True, max_size=900, dims=DIMS, stores=STORES, zero_rows=3, k4_weight=0.0, workers=0):
+    """-> (mismatches, exact ties, penalty knife-edges).  workers > 0: the oracle's calls of a batch run in that many
+    processes (d = 1024 documents take seconds each)."""
+    import oracle
+    from svx.vecalign import dp_utils
+    t0 = time.time()
+    done = bad = ties = edges = 0
+    pool = oracle_pool(workers)
+    for cfg, hosts, seeds in draw_batches(cases, seed, batch, max_size, dims, stores, zero_rows, k4_weight):
+        K, amax, types, W, max_full, sample = cfg['K'], cfg['amax'], cfg['types'], cfg['W'], cfg['max_full'], cfg['sample']
+        nsamp, frac, d, store = cfg['nsamp'], cfg['frac'], cfg['d'], cfg['store']
+        nb = len(hosts)
+        devs = to_devs(hosts, store)
+        refs = pool.map_async(_oracle_job, [(hosts[i][0], hosts[i][1], types, frac, W, max_full, sample, nsamp, seeds[i])
+                                            for i in range(nb)]) if pool else None
         pb = None
         try:
             pb = dp_utils.PreparedBatch(devs, types, frac, W, max_full, sample, nsamp, rngs=[np.random.RandomState(s) for s in seeds])
@@ -113,12 +156,17 @@ def run_sweep(cases, seed, batch=8, verbose=True, max_size=900):
             res = pb.results()
         except Exception as e:  # an error must be an error on both sides
             res = e
+        if pool:
+            refs = refs.get()
         for i in range(nb):
-            try:
-                ref = oracle.vecalign(hosts[i][0].copy(), hosts[i][1].copy(), types, frac, W, max_full, sample, nsamp,
-                                      rng=np.random.RandomState(seeds[i]))
-            except Exception as e:
-                ref = e
+            if pool:
+                ref = refs[i]
+            else:
+                try:
+                    ref = oracle.vecalign(hosts[i][0].copy(), hosts[i][1].copy(), types, frac, W, max_full, sample, nsamp,
+                                          rng=np.random.RandomState(seeds[i]))
+                except Exception as e:
+                    ref = e
             ok = False
             if isinstance(res, Exception) or isinstance(ref, Exception):
                 ok = isinstance(res, Exception) and isinstance(ref, Exception)
@@ -171,6 +219,9 @@ def run_sweep(cases, seed, batch=8, verbose=True, max_size=900):
         done += nb
         if verbose and (done // nb) % 10 == 0:
             print(f"{done} cases, {bad} mismatches, {ties} exact ties, {edges} penalty knife-edges, {time.time() - t0:.0f} s", flush=True)
+    if pool:
+        pool.terminate()
+        pool.join()
     print(f"fuzz: {done} cases, {bad} mismatches, {ties} exact ties, {edges} penalty knife-edges, {time.time() - t0:.0f} s")
     return bad, ties, edges
 
@@ -191,7 +242,7 @@ def straight_oracle(orc, v0, v1, types, W, frac, sample, nsamp, seed, pen_overri
     return al, sc, pen, ks
 
 
-def run_straight_sweep(cases, seed, batch=6, verbose=True, max_size=500):
+def run_straight_sweep(cases, seed, batch=6, verbose=True, max_size=500, dims=STRAIGHT_DIMS, stores=STORES, zero_rows=2):
     """SVX_SEARCH_STRAIGHT (band around the straight diagonal; wide bands run the tile sweep, bands that cover the
     lattice are the dense mode) against the oracle on the same straight path.  -> (mismatches, exact ties)"""
     import torch
@@ -210,8 +261,8 @@ def run_straight_sweep(cases, seed, batch=6, verbose=True, max_size=500):
         sample = int(rs.choice([500, 5000, 20000]))
         nsamp = int(rs.choice([7, 100]))
         frac = float(rs.choice([0.05, 0.2, 0.5]))
-        d = int(rs.choice([32, 64, 96, 256]))
-        store = rs.choice(["f32", "bf16", "f16"])
+        d = int(rs.choice(list(dims)))
+        store = rs.choice(list(stores))
         nb = min(batch, cases - done)
         hosts, devs = [], []
         for i in range(nb):
@@ -219,7 +270,7 @@ def run_straight_sweep(cases, seed, batch=6, verbose=True, max_size=500):
             if rs.rand() < 0.1:
                 n, m = int(rs.randint(1, 12)), int(rs.randint(1, 12))
             v0, v1 = make_pair(n, m, K, d, int(rs.randint(1 << 30)), deletions=int(rs.randint(0, 6)) if min(n, m) > 12 else 0,
-                               zero_rows=int(rs.randint(0, 3)))
+                               zero_rows=int(rs.randint(0, zero_rows + 1)))
             if store == "bf16":
                 v0, v1 = round_bf16(v0), round_bf16(v1)
                 devs.append((torch.from_numpy(v0).cuda().bfloat16(), torch.from_numpy(v1).cuda().bfloat16()))
@@ -306,14 +357,26 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--max_size", type=int, default=900, help="documents have 1 .. max_size-1 segments")
     ap.add_argument("--pipeline", action="store_true", help="run the device side with the software pipeline on (svx_set_pipeline)")
+    ap.add_argument("--dims", default="", help="embedding widths to draw from, e.g. 512,1024 (default: the small widths)")
+    ap.add_argument("--stores", default="", help="storage types to draw from, e.g. bf16,f16")
+    ap.add_argument("--zero_rows", type=int, default=-1, help="most zero rows per document (default: 3, straight: 2)")
+    ap.add_argument("--k4_weight", type=float, default=0.0, help="share of batches forced to K = 4 / -a 5")
+    ap.add_argument("--workers", type=int, default=0, help="processes for the oracle side (coarse-to-fine sweep)")
     a = ap.parse_args()
+    kw = {}
+    if a.dims:
+        kw["dims"] = tuple(int(v) for v in a.dims.split(","))
+    if a.stores:
+        kw["stores"] = tuple(a.stores.split(","))
+    if a.zero_rows >= 0:
+        kw["zero_rows"] = a.zero_rows
     if a.pipeline:
         from svx import _lib
         _lib.context().set_pipeline(True)
     if a.search == "straight":
-        bad, _ = run_straight_sweep(a.cases, a.seed, min(a.batch, 6), max_size=a.max_size)
+        bad, _ = run_straight_sweep(a.cases, a.seed, min(a.batch, 6), max_size=a.max_size, **kw)
         sys.exit(1 if bad else 0)
-    bad, _, _ = run_sweep(a.cases, a.seed, a.batch, max_size=a.max_size)
+    bad, _, _ = run_sweep(a.cases, a.seed, a.batch, max_size=a.max_size, k4_weight=a.k4_weight, workers=a.workers, **kw)
     sys.exit(1 if bad else 0)
 
 

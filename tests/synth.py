@@ -4,7 +4,10 @@ rows i < k are zero.  The target is a noisy copy of the source so that a monoton
 import numpy as np
 
 
-def make_pair(N, M, K, d, seed, noise=0.5, dtype=np.float32, zero_rows=0, deletions=0):
+def make_pair(N, M, K, d, seed, noise=0.5, dtype=np.float32, zero_rows=0, deletions=0, common=0.0):
+    """common: every non-zero row gets common * |row| * u added, u one unit direction per pair (drawn from a generator
+    of its own, so the arrays with common=0 do not change): embedding-like anisotropic data, mean cosine between
+    unrelated rows = common^2 / (1 + common^2)."""
     rng = np.random.default_rng(seed)
     L = max(N, M) + K + deletions
     base = rng.standard_normal((L, d)).astype(np.float32)
@@ -27,6 +30,11 @@ def make_pair(N, M, K, d, seed, noise=0.5, dtype=np.float32, zero_rows=0, deleti
         for v in (v0, v1):
             idx = rng.choice(v.shape[1], size=min(zero_rows, v.shape[1]), replace=False)
             v[rng.integers(0, K, size=len(idx)), idx] = 0.0
+    if common:
+        u = np.random.default_rng([int(seed), 0xC0FFEE]).standard_normal(d)
+        u /= np.sqrt((u * u).sum())
+        for v in (v0, v1):
+            v += (common * np.sqrt((v.astype(np.float64) ** 2).sum(axis=-1, keepdims=True)) * u).astype(np.float32)
     if dtype == np.float16:
         return v0.astype(np.float16), v1.astype(np.float16)
     return v0, v1
