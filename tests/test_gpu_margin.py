@@ -110,7 +110,7 @@ def test_margin_scores_match_oracle(orc, margin):
 
 
 def test_large_query_block_path(orc):
-    """n >= 32768 switches the kernel to two 16-row blocks per wave; checked on a sample of rows against the
+    """n >= 16384 switches the kernel to two 16-row blocks per wave; checked on a sample of rows against the
     oracle and on all rows against the small-block path (same values, different tiling)."""
     n, N, d, k = 32768 + 77, 1500, 1024, 16
     q = unit_rows(n, d, 5, 20)
