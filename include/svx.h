@@ -191,6 +191,19 @@ int svx_knn_mean_sim(svx_ctx *ctx, const void *queries, int q_dtype, int64_t n, 
 int svx_knn_topk_merge(svx_ctx *ctx, const void *queries, int q_dtype, int64_t n, const void *db, int db_dtype,
                        int64_t n_db, int d, int k, float *topk, int first, float *mean_sim);
 
+/* index.search(x, k) itself (score_align.py:139-141), exact, with the neighbours' row ids: what svx_knn_mean_sim averages
+ * and svx_knn_topk_merge keeps, plus which database rows they are.  sims [n][k] float32 = <q_i / |q_i|, db_j> as defined
+ * above, ids [n][k] int64 = id_base + row number.  The k results of a query are the first k of the total order
+ * (similarity descending, id ascending) over all rows seen, in that order: equal similarities come out by ascending id,
+ * and of rows that tie at the k-th place the lowest ids are kept.  A query that has seen fewer than k rows carries
+ * trailing (-inf, -1) entries.
+ * first != 0: the lists start empty; otherwise they continue from (sims, ids) as an earlier call left them (database
+ * arriving shard by shard; with distinct ids the result does not depend on the order of the shards).  n_db may be
+ * smaller than k, or 0 (db may then be NULL).  d a multiple of 32, at most 1024; 1 <= k <= 64; rows and queries finite.
+ * A separate kernel (csrc/svx_search.hip); asynchronous on the context's stream, no scratch. */
+int svx_knn_search(svx_ctx *ctx, const void *queries, int q_dtype, int64_t n, const void *db, int db_dtype,
+                   int64_t n_db, int d, int k, int64_t id_base, float *sims, int64_t *ids, int first);
+
 /* score_align.py:151-160: scores[i] = <x_i/|x_i|, y_i/|y_i|> / ((mean_xy[i] + mean_yx[i]) / 2)
  * (SVX_MARGIN_RATIO) or minus it (SVX_MARGIN_DISTANCE).  x, y [n][d] of `dtype`. */
 int svx_margin_scores(svx_ctx *ctx, const void *x, const void *y, int dtype, int64_t n, int d, const float *mean_xy,

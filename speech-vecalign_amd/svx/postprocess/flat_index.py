@@ -155,6 +155,42 @@ class FlatIndex:
                                              ctypes.c_void_p(mean.data_ptr()) if want_mean else None))
         return topk, mean
 
+    # -- search with row ids (score_align.py:139-141: index.search(x, k))
+    def merge_search(self, queries, k: int, state=None, id_base: int = 0):
+        """One shard of a sharded search with ids: merge this index's rows, numbered id_base + row, into the running
+        lists `state` = (sims float32 [n, k], ids int64 [n, k]) (None: start them) -> state, updated in place.  Every
+        query's list is ordered by (similarity descending, id ascending) and holds the first k of that order over all
+        rows seen, (-inf, -1) where fewer than k were; shards may come in any order as long as their ids are distinct.
+        The shard may hold fewer than k rows, or none."""
+        ctx = self.ctx
+        t = ctx.torch
+        q = to_device_rows(ctx, queries)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"expected [n, {self.d}] queries, got {tuple(q.shape)}")
+        shape = (q.shape[0], int(k))
+        first = state is None
+        if first:
+            sims = t.empty(shape, dtype=t.float32, device=ctx.tdev)
+            ids = t.empty(shape, dtype=t.int64, device=ctx.tdev)
+        else:
+            sims, ids = state
+            for name, a, dt in (("sims", sims, t.float32), ("ids", ids, t.int64)):
+                if not hasattr(a, "data_ptr") or tuple(a.shape) != shape or a.dtype != dt or not a.is_contiguous() or a.device != q.device:
+                    raise ValueError(f"state {name} must be a contiguous {str(dt).split('.')[-1]} [{shape[0]}, {shape[1]}] tensor on {q.device}")
+        db = self.rows
+        ctx.check(ctx.lib.svx_knn_search(ctx.h, ctypes.c_void_p(q.data_ptr()), _torch_dtype_code(t, q.dtype), int(q.shape[0]),
+                                         ctypes.c_void_p(db.data_ptr() if db.shape[0] else None), self.code, int(db.shape[0]),
+                                         self.d, int(k), int(id_base), ctypes.c_void_p(sims.data_ptr()), ctypes.c_void_p(ids.data_ptr()),
+                                         int(first)))
+        return sims, ids
+
+    def search(self, queries, k: int, l2: bool = False):
+        """faiss' index.search(queries, k) -> (D, I) device tensors, float32 [n, k] and int64 [n, k] row numbers (-1 where
+        the index has fewer than k rows).  l2=False: D = cosine similarities, descending.  l2=True: D = 2 - 2 sim, ascending:
+        the squared L2 distances IndexFlatL2.search returns for unit rows (score_align.py:139-148 averages them)."""
+        sims, ids = self.merge_search(queries, k)
+        return (2.0 - 2.0 * sims if l2 else sims), ids
+
     # -- files
     @classmethod
     def read(cls, path, storage: str = "fp16", device=None) -> "FlatIndex":
