@@ -169,6 +169,7 @@ int64_t svx_format_alignments(const int32_t *rows, const double *scores, int64_t
 
 #define SVX_MARGIN_RATIO 0
 #define SVX_MARGIN_DISTANCE 1
+#define SVX_MARGIN_ABSOLUTE 2 /* score = similarity; accepted by svx_margin_candidates only */
 
 /* populate_index: out[i] = rows[i] / |rows[i]| (faiss.normalize_L2, prep_index.py:180) stored as
  * out_dtype (SVX_F16 | SVX_BF16).  rows [n][d] of `dtype`; d a multiple of 32, at most 1024. */
@@ -208,6 +209,40 @@ int svx_knn_search(svx_ctx *ctx, const void *queries, int q_dtype, int64_t n, co
  * (SVX_MARGIN_RATIO) or minus it (SVX_MARGIN_DISTANCE).  x, y [n][d] of `dtype`. */
 int svx_margin_scores(svx_ctx *ctx, const void *x, const void *y, int dtype, int64_t n, int d, const float *mean_xy,
                       const float *mean_yx, int margin, float *scores);
+
+/* ---- margin-based mining over two Flat databases (csrc/svx_mine.hip) ----------------------
+ * Artetxe & Schwenk, https://aclanthology.org/P19-1309 sec. 3, as LASER's mine_bitexts.py runs it: every row of one
+ * side is searched in the other (svx_knn_search), its k neighbours are re-scored with the margin and the best one is
+ * taken.  The operation order below is part of the contract: the results are defined bit for bit. */
+
+/* mean[i] = (((s[i][0] + s[i][1]) + ...) + s[i][k-1]) / (float)k, fp32, j ascending: the mean similarity of a
+ * query to its k neighbours from the lists svx_knn_search left (sims [n][k]).  -inf entries propagate.  1 <= k <= 64.
+ * Asynchronous on the context's stream, no scratch. */
+int svx_knn_list_means(svx_ctx *ctx, const float *sims, int64_t n, int k, float *mean);
+
+/* Candidate scoring of margin-based mining (P19-1309 sec. 3; LASER score_candidates + argmax):
+ *   b = (mean_q[i] + mean_db[ids[i][j] - id_base]) * 0.5f
+ *   scores[i][j] = sims[i][j] / b   (SVX_MARGIN_RATIO)
+ *                | sims[i][j] - b   (SVX_MARGIN_DISTANCE)
+ *                | sims[i][j]       (SVX_MARGIN_ABSOLUTE; mean_q and mean_db are not read and may be NULL)
+ * each operation rounded to fp32 on its own, the division correctly rounded.  sims, ids [n][k] as svx_knn_search left
+ * them; mean_q [n], mean_db [n_db] = svx_knn_list_means of the lists of the two directions.
+ * An id of -1, or one outside [id_base, id_base + n_db), is never dereferenced and scores -inf.
+ * best starts as (-inf, -1); candidate j replaces it when scores[i][j] > best_score, j ascending.
+ * So ties go to the lowest j (= higher similarity, then lower id), and NaN / -inf never win.
+ * best_id [n] int64 (the id as it stands in ids), best_score [n]; scores [n][k] may be NULL.  1 <= k <= 64.
+ * Asynchronous on the context's stream, no scratch. */
+int svx_margin_candidates(svx_ctx *ctx, const float *sims, const int64_t *ids, int64_t n, int k, const float *mean_q,
+                          const float *mean_db, int64_t n_db, int64_t id_base, int margin, float *scores, int64_t *best_id,
+                          float *best_score);
+
+/* The sequential greedy pass of LASER's `max` retrieval (mine_bitexts.py: seen_src / seen_trg).  HOST pointers, no device
+ * work, callable from any thread.  order[p], p < n_cand: candidate indices in output order; src[], tgt[] [n_cand]: their
+ * rows, src[c] < n_src, tgt[c] < n_tgt.  Keeps candidate c = order[p] iff neither src[c] nor tgt[c] was kept before;
+ * writes the kept c's to out [n_cand] in order.  Returns the count, or -SVX_ERR_ARG (null pointer, negative count, an
+ * index out of range). */
+int64_t svx_mine_greedy(const int64_t *order, int64_t n_cand, const int64_t *src, const int64_t *tgt, int64_t n_src,
+                        int64_t n_tgt, int64_t *out);
 
 /* ---- the whole of dp_utils.vecalign() for a batch of document pairs -------------------- */
 

@@ -1,7 +1,7 @@
 // svx_host.hip -- host-side (CPU) pieces of the C ABI that sit in front of and behind the kernels when a
 // process has to feed a GPU at hundreds of document pairs per second: the sampled row indices, the candidate
-// index table of a document, and the text of an alignment file.  Plain C++; nothing here touches the device,
-// and every function may be called from any thread (ctypes releases the GIL around them).
+// index table of a document, the text of an alignment file, and the greedy pass of margin-based mining.  Plain C++;
+// nothing here touches the device, and every function may be called from any thread (ctypes releases the GIL around them).
 //
 // Reference semantics (paths relative to the reference repository):
 //   np.random.choice call order      svecalign/vecalign/dp_utils.py:301-302, 345-348  
@@ -9,6 +9,7 @@
 //   read_in_embeddings (key -> first row) svecalign/utils/embedding_utils.py:79-103
 //   load_ignore_index_file           svecalign/vecalign/vecalign.py:187-195
 //   print_alignments                 svecalign/vecalign/vecalign.py:174-184
+//   svx_mine_greedy                  no counterpart in the reference: the seen_src / seen_trg loop of LASER's mine_bitexts.py
 #include <errno.h>
 #include <stdio.h>
 #include <string.h>
@@ -301,6 +302,23 @@ int64_t svx_format_alignments(const int32_t* rows, const double* scores, int64_t
         put("\n", 1);
     }
     return w;  // bytes needed (written when they fit)
+}
+
+int64_t svx_mine_greedy(const int64_t* order, int64_t n_cand, const int64_t* src, const int64_t* tgt, int64_t n_src, int64_t n_tgt,
+                        int64_t* out) {
+    if (n_cand < 0 || n_src < 0 || n_tgt < 0 || (n_cand > 0 && (!order || !src || !tgt || !out))) return -SVX_ERR_ARG;
+    std::vector<uint8_t> seen_src((size_t)n_src, 0), seen_tgt((size_t)n_tgt, 0);
+    int64_t kept = 0;
+    for (int64_t p = 0; p < n_cand; p++) {
+        const int64_t c = order[p];
+        if (c < 0 || c >= n_cand) return -SVX_ERR_ARG;
+        const int64_t s = src[c], t = tgt[c];
+        if (s < 0 || s >= n_src || t < 0 || t >= n_tgt) return -SVX_ERR_ARG;
+        if (seen_src[(size_t)s] || seen_tgt[(size_t)t]) continue;
+        seen_src[(size_t)s] = seen_tgt[(size_t)t] = 1;
+        out[kept++] = c;
+    }
+    return kept;
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("SVX_LIB") or os.path.join(_HERE, "libsvx.so")   # (SV
 SVX_F32, SVX_F16, SVX_BF16 = 0, 1, 2
 SVX_MAX_TYPES = 128
 SVX_MAX_LEVELS = 16
-SVX_MARGIN_RATIO, SVX_MARGIN_DISTANCE = 0, 1
+SVX_MARGIN_RATIO, SVX_MARGIN_DISTANCE, SVX_MARGIN_ABSOLUTE = 0, 1, 2
 SVX_SEARCH_COARSE_TO_FINE, SVX_SEARCH_STRAIGHT = 0, 1
 
 SVX_OK, SVX_ERR_ARG, SVX_ERR_OVERLAPS, SVX_ERR_HIP, SVX_ERR_TRACEBACK = 0, 1, 2, 3, 4
@@ -93,6 +93,9 @@ _SIGS = {
     "svx_knn_topk_merge": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_int, c_vp]),
     "svx_knn_search": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_int, c_i64, c_vp, c_vp, c_int]),
     "svx_margin_scores": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_int, c_vp]),
+    "svx_knn_list_means": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),
+    "svx_margin_candidates": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp]),
+    "svx_mine_greedy": (c_i64, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "svx_mt19937_choice": (c_int, [c_vp, ctypes.POINTER(ctypes.c_int32), c_i64, c_i64, c_vp]),
     "svx_norm_index_count": (c_i64, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "svx_knob_index_count": (c_i64, [c_int, c_int, c_int, c_int]),
