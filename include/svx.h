@@ -306,7 +306,11 @@ int svx_align_batch(svx_ctx *ctx, const svx_align_params *params, const svx_pair
 /* Per-level intermediates of the LAST svx_align_batch call on this context -- the entries of the `stack` the reference
  * returns (dp_utils.py:412-537) -- as device pointers into the context's scratch arena (valid until the next call;
  * the scalar fields are read back, which synchronises the stream).  Pointers are NULL for what a level does not have
- * (the coarsest level of a pyramid only has normalisers, penalty and alignments; the tile sweep keeps no cost array). */
+ * (the coarsest level of a pyramid only has normalisers, penalty and alignments; the tile sweep keeps no cost array).
+ * a_b_csum and the back-pointers hold the reference's values on every band cell that is a node of the lattice
+ * (0 <= x <= size0, 0 <= y <= size1; +inf / -42 where unreachable).  The band kernels (band <= 64 cells, and every
+ * coarse-to-fine level) also fill the band cells outside the lattice like the reference, +inf / -42; the tile sweep
+ * stores lattice nodes only, and those cells are UNSPECIFIED there (nothing reads them). */
 typedef struct svx_level_view {
     int32_t size0, size1, k0, k1;   /* rows and overlap layers of the two sides at this depth */
     int32_t n_types, band;          /* alignment types of this depth, cells per diagonal (2 * width_over2) */

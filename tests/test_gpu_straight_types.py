@@ -6,31 +6,11 @@ over the whole documents): identical spans, scores within 1e-4."""
 import numpy as np
 import pytest
 
+from dp_ref import many_to_one_types, straight_oracle   # (shared with test_gpu_dp_ties.py)
 from synth import alignment_types, make_pair, round_bf16
 
 pytestmark = pytest.mark.gpu
 SCORE_TOL = 1e-4
-
-
-def straight_oracle(orc, v0, v1, types, W, seed):
-    """make_sparse_costs + sparse_dp + sparse_traceback on the straight path, depth-0 norms and penalty (oracle)."""
-    N, M = v0.shape[1], v1.shape[1]
-    a, b = v0.copy(), v1.copy()
-    orc.make_norm1(a)
-    orc.make_norm1(b)
-    rs = np.random.RandomState(seed)
-    n0, n1 = orc.compute_norms(a, b, 100, rs), orc.compute_norms(b, a, 100, rs)
-    pen, _ = orc.make_del_penalty(a[0], b[0], n0[0], n1[0], 20000, 0.2, rs)
-    path = orc.search_path([(list(range(N)), list(range(M)))], False, N, M)
-    f, bo = orc.make_sparse_costs(a, b, n0, n1, path, types, W)
-    return orc.sparse_traceback(*orc.sparse_dp(f, bo, types, pen, N, M), N, M)
-
-
-def many_to_one_types(m):
-    from svx.vecalign.vecalign import resolve_search_params
-    types, sk, tk, _ = resolve_search_params(10, m, 5)
-    assert (sk, tk) == (m, 1)
-    return types
 
 
 def storage(v, dt):
