@@ -303,6 +303,39 @@ int64_t svx_knob_count(int n_l, int m_l, int costs_sample_size);
  * ['final_alignments'] and ['alignment_scores'] per pair. */
 int svx_align_batch(svx_ctx *ctx, const svx_align_params *params, const svx_pair *pairs, int n_pairs);
 
+/* ---- margin from candidate rows: the alignment rows of a batch -> the inputs of the margin half -------------
+ * svecalign/postprocess/embed_align.py embeds the audio span of every mined alignment again, from the start of its first
+ * segment to the end of its last (svecalign/utils/file_utils.py:158-163).  For an alignment of at most k0 x k1 segments
+ * that span is the line "<start> <end>" of the candidate file and its embedding is the candidate row
+ * vecs0[x_len-1][x_start+x_len-1] the DP has just read, so the two row matrices svx_unit_rows / svx_knn_mean_sim /
+ * svx_margin_scores expect are gathered on the device, with no encoder and no host round trip (csrc/svx_alignrows.hip).
+ *
+ * Read per pair (pairs: HOST array): vecs0, vecs1, n, m, k0, k1, align, scores, info -- as an earlier svx_align_batch on this
+ * context's stream left them, or as any caller filled them; nothing else of svx_pair is read.  align and scores hold
+ * n + m + 2 rows; rows past that are never read.  vecs0 / vecs1 and the row buffers below are 16-byte aligned.
+ *
+ * Row r of pair p is KEPT iff  info[1] == 0 and 0 <= r < info[0];  1 <= x_len <= k0 and 1 <= y_len <= k1 (deletions and
+ * anything wider than a candidate go);  0 <= x_start, x_start + x_len <= n, 0 <= y_start, y_start + y_len <= m;  and
+ * scores[r] <= max_score as a plain double comparison (NaN fails; max_score = +inf keeps every non-deletion).  A row that
+ * is not kept is never used to form an address: a failed pair may hold garbage.
+ *
+ * Kept rows are numbered j = 0, 1, ... in (pair ascending, r ascending) order.  At j:
+ *   x_rows[j] = vecs0[x_len-1][x_start+x_len-1][:], y_rows[j] = vecs1[y_len-1][y_start+y_len-1][:], copied bit for bit
+ *               ([cap][d] of `dtype`);
+ *   src[j]    = (p, r)                                                   ([cap][2] int32);
+ *   x_unit[j], y_unit[j] = bit for bit what svx_unit_rows(..., unit_dtype) writes for that row, a zero row stays zero
+ *               ([cap][d] fp16 | bf16; both pointers or neither).
+ * *count (device, [1]) = the number of kept rows, also when it exceeds cap; only j < cap is written and nothing else of
+ * the output buffers is touched.  cap = 0 or n_pairs = 0 is legal, the buffers may then be NULL.
+ * d: with unit rows a multiple of 32, at most 1024 (the margin entries' rule); without them a multiple of 8, at most
+ * SVX_MAX_DIM.  A violation, a null argument or an unknown dtype returns SVX_ERR_ARG with text and queues nothing.
+ * Asynchronous on the context's stream, no host synchronisation; it calls svx_flush first, so with the software pipeline
+ * on it still sees complete outputs.  Scratch (a copy of the descriptors, a chunk table, per-chunk counts and offsets)
+ * lives in a grow-only buffer of the context's own, not in the arena -- the views of svx_debug_level stay valid --, is
+ * counted in svx_scratch_bytes and is uploaded through pinned staging like svx_align_batch's descriptors. */
+int svx_alignment_rows(svx_ctx *ctx, int dtype, int d, const svx_pair *pairs, int n_pairs, double max_score, int64_t cap,
+                       void *x_rows, void *y_rows, void *x_unit, void *y_unit, int unit_dtype, int32_t *src, int64_t *count);
+
 /* Per-level intermediates of the LAST svx_align_batch call on this context -- the entries of the `stack` the reference
  * returns (dp_utils.py:412-537) -- as device pointers into the context's scratch arena (valid until the next call;
  * the scalar fields are read back, which synchronises the stream).  Pointers are NULL for what a level does not have

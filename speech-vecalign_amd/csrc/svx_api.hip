@@ -148,6 +148,10 @@ int svx_create(int device_id, svx_ctx** out) {
     c->arena_used = 0;
     c->err[0] = 0;
     c->profiling = 0;
+    c->rows_buf = nullptr;
+    c->rows_bytes = 0;
+    c->rows_turn = 0;
+    for (int i = 0; i < 2; i++) { c->rows_pin[i] = nullptr; c->rows_pin_cap[i] = 0; c->rows_up[i] = nullptr; c->rows_up_valid[i] = 0; }
     for (int i = 0; i < S_COUNT; i++) { c->ms[i] = -1.0; c->launches[i] = 0; }
     c->pipeline = 0;
     c->last_split = 0;
@@ -169,6 +173,7 @@ int svx_destroy(svx_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     if (c->chain_ready) (void)hipStreamSynchronize(c->chain);
     if (ctx->arena) (void)hipFree(ctx->arena);
+    svxl_alignrows_release(ctx);
     drop_pending(c);
     for (auto& r : c->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     if (c->side_ready) {
@@ -212,7 +217,7 @@ const char* svx_last_error(const svx_ctx* ctx) { return ctx ? ctx->err : g_err; 
 int64_t svx_scratch_bytes(const svx_ctx* ctx) {
     if (!ctx) return 0;
     const svx_ctx_ext* c = static_cast<const svx_ctx_ext*>(ctx);
-    return (int64_t)(ctx->arena_bytes + c->half[0].arena_bytes + c->half[1].arena_bytes);
+    return (int64_t)(ctx->arena_bytes + c->half[0].arena_bytes + c->half[1].arena_bytes + ctx->rows_bytes);
 }
 
 int svx_set_pipeline(svx_ctx* ctx, int on) {

@@ -243,6 +243,15 @@ struct svx_ctx {
     size_t arena_used;
     char err[512];
     int profiling;
+    // svx_alignment_rows (svx_alignrows.hip): its descriptor copy, chunk table, counts and offsets live in a grow-only
+    // buffer of their own (the arena keeps the views of svx_debug_level), uploaded through two pinned buffers in turn
+    char* rows_buf;
+    size_t rows_bytes;
+    char* rows_pin[2];
+    size_t rows_pin_cap[2];
+    hipEvent_t rows_up[2];
+    int rows_up_valid[2];
+    int rows_turn;
 };
 
 int svx_fail(svx_ctx* ctx, int code, const char* fmt, ...);
@@ -258,6 +267,8 @@ int svx_fail(svx_ctx* ctx, int code, const char* fmt, ...);
     } while (0)
 
 // ---- kernel launchers (defined in the .hip files) ---------------------------------------
+// alignment rows (svx_alignrows.hip)
+void svxl_alignrows_release(svx_ctx*);
 // rows / pyramid (svx_rows.hip)
 int svxl_make_norm1(svx_ctx*, float* vecs, int64_t rows, int d);
 int svxl_pairsum(svx_ctx*, const float* vecs, int k, int n, int d, float* half, float* part, int nblk);

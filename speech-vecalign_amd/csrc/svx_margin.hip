@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "svx_knn.h"
+#include "svx_unit.h"
 
 // Register top-k (k <= 16).  The kept list of query row (b, 4 lg + r) lives in hp[b][r] of the 16 lanes of
 // lane group lg -- the lanes that also receive that row's similarities from the MFMA -- and th[b][r] is its
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(256) void k_margin_scores(const typename QE::storag
     }
 }
 
-// rows -> unit norm -> fp16 / bf16 (what populate_index keeps, prep_index.py:153-185)
+// rows -> unit norm -> fp16 / bf16 (what populate_index keeps, prep_index.py:153-185); the arithmetic is svx_unit.h's
 template <typename QE>
 __global__ __launch_bounds__(256) void k_unit_rows(const typename QE::storage* __restrict__ in, long n, int d, int bf,
                                                    uint16_t* __restrict__ out) {
@@ -340,20 +341,13 @@ __global__ __launch_bounds__(256) void k_unit_rows(const typename QE::storage* _
     for (int c = lane * 8; c < d; c += 64 * 8) {
         float a[8];
         load8<QE>(r + c, a);
-#pragma unroll
-        for (int j = 0; j < 8; j++) ss += a[j] * a[j];
+        ss = unit_sumsq8(ss, a);
     }
-    ss = wave_sum(ss);
-    const float inv = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
+    const float inv = unit_scale(wave_sum(ss));
     for (int c = lane * 8; c < d; c += 64 * 8) {
         float a[8];
         load8<QE>(r + c, a);
-        uint4 v;
-        v.x = pack_pair(a[0] * inv, a[1] * inv, bf != 0);
-        v.y = pack_pair(a[2] * inv, a[3] * inv, bf != 0);
-        v.z = pack_pair(a[4] * inv, a[5] * inv, bf != 0);
-        v.w = pack_pair(a[6] * inv, a[7] * inv, bf != 0);
-        *reinterpret_cast<uint4*>(out + i * (long)d + c) = v;
+        *reinterpret_cast<uint4*>(out + i * (long)d + c) = unit_pack8(a, inv, bf != 0);
     }
 }
 

@@ -107,6 +107,7 @@ _SIGS = {
     "svx_num_levels": (c_int, [c_int, c_int, c_int]),
     "svx_knob_count": (c_i64, [c_int, c_int, c_int]),
     "svx_align_batch": (c_int, [c_vp, ctypes.POINTER(AlignParams), ctypes.POINTER(Pair), c_int]),
+    "svx_alignment_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), c_int, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "svx_debug_level": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(LevelView)]),
     "svx_copy_to_host": (c_int, [c_vp, c_vp, c_vp, c_i64]),
     "svx_set_profiling": (c_int, [c_vp, c_int]),

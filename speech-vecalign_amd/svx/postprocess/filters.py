@@ -5,10 +5,13 @@ Same behaviour, file formats and defaults as the reference scripts:
   concat_consecutive  svecalign/postprocess/concat_aligns.py:56-110   (runs of up to `max_num_align` connected
                                                                         alignments, silence and duration limits)
   keep_by_duration    svecalign/postprocess/filter_by_dur.py:43-71    (both sides at least `min_frames` long)
+  cost_limit          the double threshold that keeps what keep_by_cost keeps from the '%.6f' text (svx_alignment_rows)
 Each has the reference's command line in its own module (filter_by_cost.py, concat_aligns.py, filter_by_dur.py).
 """
 import logging
+import math
 import os
+import struct
 from pathlib import Path
 from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 
@@ -36,6 +39,30 @@ def keep_by_cost(in_path: str, out_path: str, max_cost: Optional[float] = None, 
     logger.debug(f"{os.path.basename(in_path)} || Threshold: {max_cost} || #Kept: {len(kept)}/{len(rows)} "
                  f"|| #Low quality: {len(rows) - len(kept) - n_del} || #Deletions: {n_del}")
     return len(kept) / len(rows)
+
+
+def cost_limit(max_cost: float) -> float:
+    """The largest double v >= 0 with float("%.6f" % v) <= max_cost.
+
+    keep_by_cost does not compare the DP's double: it compares the value parsed back from the '%.6f' text of the
+    alignment file (0.0078125 prints as 0.007812).  A device-side `score <= cost_limit(max_cost)` (svx_alignment_rows'
+    max_score) therefore keeps exactly the lines `filter_by_cost --max_cost` keeps from the file written from the same
+    doubles.  Python's formatting is correctly rounded, hence monotone in v, and non-negative doubles are ordered like
+    their bit patterns: the limit is found by bisection over those."""
+    max_cost = float(max_cost)
+    if math.isnan(max_cost) or max_cost < 0:
+        raise ValueError(f"max_cost {max_cost}: must be >= 0")
+    if math.isinf(max_cost):
+        return max_cost
+    as_double = lambda bits: struct.unpack("<d", struct.pack("<q", bits))[0]
+    lo, hi = 0, struct.unpack("<q", struct.pack("<d", math.inf))[0]   # passes / fails
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if float("%.6f" % as_double(mid)) <= max_cost:
+            lo = mid
+        else:
+            hi = mid
+    return as_double(lo)
 
 
 def concat_consecutive(alignments: Sequence[Alignment], src_frames: Sequence[Tuple[int, int]],

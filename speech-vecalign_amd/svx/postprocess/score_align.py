@@ -84,14 +84,19 @@ def compute_sim_with_nonflat_idx(idx_x: FlatIndex, idx_y: FlatIndex, x: np.ndarr
 
 
 def global_margin_scores(x_local, y_local, k: int = 16, margin: str = "ratio", storage: str = "fp16", group=None,
-                         device=None, exchange: str = "allgather"):
+                         device=None, exchange: str = "allgather", x_unit=None, y_unit=None):
     """Each rank passes the embeddings of ITS alignments; the databases are the union over ranks, the scores come
     back for the local rows only.  exchange="allgather" (default): one RCCL all-gather, then a local search of the
     whole corpus.  exchange="ring": the normalised fp16 shards travel round the ring of ranks and every rank merges
     its queries' top-k shard by shard (`ring_shards`, svx_knn_topk_merge) -- two shards of HBM per GPU, transfer
     overlapped with search; it stays opt-in until a multi-GPU run of tests/test_gpu_margin.py::
     test_global_margin_over_rccl is on record (the one-GPU box can only run it with a world of one).  Both give the
-    k nearest neighbours over the whole corpus."""
+    k nearest neighbours over the whole corpus.
+    x_unit, y_unit (both or neither): the local rows already unit-normalised and rounded to `storage`, as
+    svx_alignment_rows / svx_unit_rows write them; they become this rank's share of the databases (add_unit_rows) and
+    nothing is normalised twice.  With them, fewer than k rows on a side is a ValueError on either exchange."""
+    if (x_unit is None) != (y_unit is None):
+        raise ValueError("x_unit and y_unit are given together or not at all")
     if exchange not in ("ring", "allgather"):
         raise ValueError(f"exchange {exchange!r}: 'ring' or 'allgather'")
     if margin not in MARGINS:
@@ -100,13 +105,21 @@ def global_margin_scores(x_local, y_local, k: int = 16, margin: str = "ratio", s
     t = ctx.torch
     d = int(x_local.shape[1])
     idx_x, idx_y = FlatIndex(d, storage, device), FlatIndex(d, storage, device)
-    idx_x.add(x_local)
-    idx_y.add(y_local)
+    if x_unit is not None:
+        for idx, unit, rows in ((idx_x, x_unit, x_local), (idx_y, y_unit, y_local)):
+            if tuple(unit.shape) != tuple(rows.shape) or unit.dtype != idx.tdtype:
+                raise ValueError(f"unit rows {tuple(unit.shape)} {unit.dtype}: expected {tuple(rows.shape)} in {storage}")
+            idx.add_unit_rows(unit)
+    else:
+        idx_x.add(x_local)
+        idx_y.add(y_local)
     if exchange == "allgather":
         gx, gy = FlatIndex(d, storage, device), FlatIndex(d, storage, device)
         gx.add_unit_rows(all_gather_rows(idx_x.rows, group))
         gy.add_unit_rows(all_gather_rows(idx_y.rows, group))
         ctx.sync()
+        if x_unit is not None and min(gx.ntotal, gy.ntotal) < k:
+            raise ValueError(f"the corpus has {min(gx.ntotal, gy.ntotal)} rows on one side, fewer than k = {k}")
         return margin_scores_device(gx, gy, x_local, y_local, k, margin)
     xd, yd = to_device_rows(ctx, x_local), to_device_rows(ctx, y_local)
     assert xd.shape == yd.shape, f"{tuple(xd.shape)} {tuple(yd.shape)}"

@@ -11,6 +11,12 @@ pair at a time), --seed (per-pair sampling streams derived from (seed, pair inde
 depend on batch size or shard count; without it the global numpy stream is consumed pair after
 pair exactly like the reference), --skip_existing, --rank/--n_shard (default from torchrun's
 RANK/WORLD_SIZE: one process per GPU, pairs split by cost, no collective needed).
+
+--margin_dir DIR adds the global margin score of every alignment that is no deletion (and passes --max_cost), without
+the reference's second pass of the speech encoder (postprocess/embed_align.py): the embedding of an un-concatenated
+alignment's span is the candidate row the DP has just read, so after every batch svx_alignment_rows gathers those rows
+on the device, and after the last batch they are scored against the union over ranks (global_margin_scores).  Under
+torch.distributed.run the ranks form a process group for that exchange; the alignment files do not change.
 """
 import argparse
 import dataclasses
@@ -61,7 +67,23 @@ def parse_args(argv=None):
     p.add_argument("--skip_existing", action="store_true", default=False, help="do not recompute existing outputs")
     p.add_argument("--rank", type=int, default=int(os.environ.get("RANK", 0)))
     p.add_argument("--n_shard", type=int, default=int(os.environ.get("WORLD_SIZE", 1)))
-    return p.parse_args(argv)
+    p.add_argument("--margin_dir", type=str, default=None,
+                   help="also write {margin_dir}/{src}-{tgt}/{s}-{t}.txt: one line src_ids:tgt_ids:margin per alignment that is no "
+                        "deletion (and passes --max_cost), scored against the rows of all ranks.  The rows stay on the device until "
+                        "the last batch: (e + 2) * d bytes per kept alignment and side, e = the embeddings' element size")
+    p.add_argument("--margin", choices=["ratio", "distance"], default="ratio", help="--margin_dir: margin function (https://aclanthology.org/P19-1309)")
+    p.add_argument("--k", type=int, default=16, help="--margin_dir: number of nearest neighbours")
+    p.add_argument("--max_cost", type=float, default=None,
+                   help="--margin_dir: keep the alignments filter_by_cost --max_cost keeps from the alignment file (default: every non-deletion)")
+    p.add_argument("--margin_storage", choices=["fp16", "bf16"], default="fp16", help="--margin_dir: storage of the unit-norm database rows")
+    p.add_argument("--margin_exchange", choices=["allgather", "ring"], default="allgather",
+                   help="--margin_dir: how the ranks' rows meet (global_margin_scores)")
+    args = p.parse_args(argv)
+    if args.margin_dir is not None and args.skip_existing:
+        p.error("--margin_dir needs the rows of every pair: it cannot be combined with --skip_existing")
+    if args.max_cost is not None and args.max_cost < 0:
+        p.error("--max_cost must be >= 0")
+    return args
 
 
 @dataclasses.dataclass
@@ -139,6 +161,78 @@ def _write_result(path: str, rows: np.ndarray, scores: np.ndarray):
     Path(tmp).replace(path)
 
 
+def _write_text(path: str, text: str):
+    tmp = path + ".tmp"
+    with open(tmp, "w") as fp:
+        fp.write(text)
+    Path(tmp).replace(path)
+
+
+class MarginRows:
+    """--margin_dir: the kept alignments' rows of every batch of this rank, on the device until the last batch."""
+
+    def __init__(self, args):
+        from ..postprocess.filters import cost_limit
+        self.args = args
+        self.limit = float("inf") if args.max_cost is None else cost_limit(args.max_cost)
+        self.parts = []    # per batch: (x_rows, y_rows, x_unit, y_unit) trimmed to the kept rows
+        self.files = []    # per pair with kept rows, in row order: (file name, ["src_ids:tgt_ids", ...])
+        self.d = self.dtype = None
+
+    def gather(self, pb):
+        """Behind pb.run() on the compute stream (asynchronous)."""
+        pb.alignment_rows(self.limit, self.args.margin_storage)
+
+    def collect(self, chunk, pb, info, align, offs):
+        """After the batch's fetch event: trim the row buffers to the count and note the ids of the kept alignments."""
+        cnt = pb.rows_count()
+        x_rows, y_rows, x_unit, y_unit, _, _ = pb.rows
+        self.d, self.dtype = int(x_rows.shape[1]), x_rows.dtype
+        pb.rows = None
+        if cnt == 0:
+            return
+        self.parts.append(tuple(t[:cnt].clone() for t in (x_rows, y_rows, x_unit, y_unit)))
+        src = pb.h_rows[1].numpy()[:cnt]
+        bounds = np.searchsorted(src[:, 0], np.arange(len(chunk) + 1))
+        for i, p in enumerate(chunk):
+            rows = align[int(offs[i]) + src[bounds[i]:bounds[i + 1], 1]]
+            if len(rows):
+                self.files.append((os.path.basename(p.output_path),
+                                   ["%s:%s" % (list(range(r[0], r[0] + r[1])), list(range(r[2], r[2] + r[3]))) for r in rows.tolist()]))
+
+    def finish(self, ctx):
+        """Score this rank's rows against the union over ranks and write the margin files."""
+        import torch
+        from ..postprocess.score_align import _dist_rank_world, global_margin_scores
+        a = self.args
+        _, world, _ = _dist_rank_world()
+        udt = torch.float16 if a.margin_storage == "fp16" else torch.bfloat16
+        if world > 1:   # a rank without pairs still takes part in the exchange: it needs the others' row shape
+            import torch.distributed as dist
+            codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+            shape = torch.tensor([self.d or 0, codes.get(self.dtype, 0)], dtype=torch.int64, device=ctx.tdev)
+            dist.all_reduce(shape, op=dist.ReduceOp.MAX)
+            if self.d is None:
+                self.d, self.dtype = int(shape[0]), {v: k for k, v in codes.items()}[int(shape[1])]
+        if not self.d:
+            return
+        if self.parts:
+            x, y, xu, yu = (torch.cat(ts, dim=0) for ts in zip(*self.parts))
+        else:
+            x, y = (torch.empty((0, self.d), dtype=self.dtype, device=ctx.tdev) for _ in range(2))
+            xu, yu = (torch.empty((0, self.d), dtype=udt, device=ctx.tdev) for _ in range(2))
+        self.parts = []
+        scores = global_margin_scores(x, y, k=a.k, margin=a.margin, storage=a.margin_storage, exchange=a.margin_exchange,
+                                      x_unit=xu, y_unit=yu).cpu().numpy()
+        out_dir = Path(a.margin_dir) / f"{a.src_lang}-{a.tgt_lang}"
+        out_dir.mkdir(parents=True, exist_ok=True)
+        at = 0
+        for name, ids in self.files:   # `src:tgt:score` as score_align.write_to_output prints it
+            _write_text((out_dir / name).as_posix(), "".join(f"{s}:{scores[at + j]}\n" for j, s in enumerate(ids)))
+            at += len(ids)
+        assert at == scores.shape[0], f"{at}, {scores.shape}"
+
+
 def _prepare_pair(p: VecalignData, args, src_k: int, tgt_k: int):
     """Host half of one document pair (runs on a pool thread; the heavy parts are native / I/O and release the
     GIL): candidate index tables from the segment and candidate files, embedding files into pinned memory."""
@@ -166,7 +260,10 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
     from ..vecalign.dp_utils import PreparedBatch
     types, src_k, tgt_k, width_over2 = resolve_search_params(args.alignment_max_size, None, args.search_buffer_size)
     todo = [p for p in pairs if not (args.skip_existing and Path(p.output_path).exists())]
+    margin = MarginRows(args) if getattr(args, "margin_dir", None) is not None else None
     if not todo:
+        if margin is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:   # the other ranks wait for this one in the exchange
+            margin.finish(_lib.context())
         return
     ctx = _lib.context()
     dev = ctx.tdev
@@ -192,6 +289,8 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
         chunk, pb, ev, held = job
         ev.synchronize()
         info, align, scores, _, offs = pb.raw_results()
+        if margin is not None:
+            margin.collect(chunk, pb, info, align, offs)
         writes = []
         for i, p in enumerate(chunk):
             o, cnt = int(offs[i]), int(info[i, 0])
@@ -232,6 +331,8 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
             pb = PreparedBatch(docs, types, args.del_percentile_frac, w2, args.max_size_full_dp,
                                args.costs_sample_size, args.num_samps_for_norm, rngs=rngs, search=search)
             pb.run()
+            if margin is not None:
+                margin.gather(pb)
             ev = pb.fetch_async()
             job = (chunk, pb, ev, (prepared, dev_in))
             # ---- while this batch computes: hand the previous batch to the writers
@@ -248,6 +349,8 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
         for writes, _ in pending_writes:
             for w in writes:
                 w.get()
+        if margin is not None:
+            margin.finish(ctx)
     except BaseException:
         # a failed pair must not leave threads behind: drop the reads still queued, let the writes already handed
         # over finish (their files are complete or absent: write-then-rename), then re-raise

@@ -269,6 +269,7 @@ class PreparedBatch:
         """Launch the whole pipeline for the batch (asynchronous on the current torch stream)."""
         ctx = self.ctx
         ctx.use_current_stream()
+        self.rows = self.h_rows = None   # (alignment_rows() of an earlier run)
         try:
             ctx.check(ctx.lib.svx_align_batch(ctx.h, ctypes.byref(self.prm), self.cpairs, len(self.vecs)))
         finally:   # a call that fails half way may already have queued work that reads this batch
@@ -279,14 +280,58 @@ class PreparedBatch:
         whatever follows on the current stream."""
         self.ctx.flush()
 
+    def alignment_rows(self, max_score=float("inf"), unit_storage="fp16"):
+        """The margin half's inputs for the alignments of the last run() (svx_alignment_rows, include/svx.h): the candidate
+        rows of every alignment that is no deletion and whose score is <= max_score, in (pair, alignment) order.
+        -> device tensors (x_rows, y_rows [cap, d] of the input dtype, x_unit, y_unit [cap, d] unit-norm rows in
+        `unit_storage` = "fp16" | "bf16" (None: no unit rows, both are None), src [cap, 2] int32 = (pair, alignment row),
+        count [1] int64).  cap = sum over pairs of min(n, m) -- a kept alignment consumes a segment on each side, so the
+        count never exceeds it; only the first `count` rows are defined.  Asynchronous on the current stream:
+        rows_count() reads `count`, and that read is the only synchronisation."""
+        if unit_storage not in ("fp16", "bf16", None):
+            raise ValueError(f"unit_storage {unit_storage!r}: 'fp16', 'bf16' or None")
+        ctx = self.ctx
+        t = ctx.torch
+        ctx.use_current_stream()
+        cap = int(sum(min(int(a.shape[1]), int(b.shape[1])) for a, b in self.vecs))
+        d, dt = int(self.prm.d), self.vecs[0][0].dtype
+        x_rows = t.empty((cap, d), dtype=dt, device=ctx.tdev)
+        y_rows = t.empty((cap, d), dtype=dt, device=ctx.tdev)
+        x_unit = y_unit = None
+        code = _lib.SVX_F16
+        if unit_storage is not None:
+            udt, code = (t.float16, _lib.SVX_F16) if unit_storage == "fp16" else (t.bfloat16, _lib.SVX_BF16)
+            x_unit = t.empty((cap, d), dtype=udt, device=ctx.tdev)
+            y_unit = t.empty((cap, d), dtype=udt, device=ctx.tdev)
+        src = t.empty((cap, 2), dtype=t.int32, device=ctx.tdev)
+        count = t.empty((1,), dtype=t.int64, device=ctx.tdev)
+        ctx.check(ctx.lib.svx_alignment_rows(ctx.h, int(self.prm.dtype), d, self.cpairs, len(self.vecs), float(max_score), cap,
+                                             _p(x_rows), _p(y_rows), _p(x_unit), _p(y_unit), code, _p(src), _p(count)))
+        self.rows = (x_rows, y_rows, x_unit, y_unit, src, count)
+        return self.rows
+
+    def rows_count(self):
+        """Number of rows alignment_rows() kept.  Uses the copy of fetch_async() when there is one (after its event);
+        otherwise this read synchronises the stream."""
+        if getattr(self, "h_rows", None) is not None:
+            return int(self.h_rows[0][0])
+        if getattr(self, "rows", None) is None:
+            raise RuntimeError("rows_count() before alignment_rows()")
+        return int(self.rows[5].item())
+
     def fetch_async(self):
         """Queue the device -> pinned-host copies of the outputs behind run() on the current stream and return
-        an event that fires when they have landed (the host pipeline formats batch i while batch i+1 computes)."""
+        an event that fires when they have landed (the host pipeline formats batch i while batch i+1 computes).
+        After alignment_rows() its `count` and `src` travel along (h_rows = (count, src))."""
         t = self.ctx.torch
         self.ctx.flush()  # (a no-op unless the pipeline is on)
         self.h_out = tuple(t.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in (self.info, self.align, self.scores, self.del_pen))
         for h, d in zip(self.h_out, (self.info, self.align, self.scores, self.del_pen)):
             h.copy_(d, non_blocking=True)
+        if getattr(self, "rows", None) is not None:
+            self.h_rows = tuple(t.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in (self.rows[5], self.rows[4]))
+            for h, d in zip(self.h_rows, (self.rows[5], self.rows[4])):
+                h.copy_(d, non_blocking=True)
         ev = t.cuda.Event()
         ev.record(t.cuda.current_stream(self.ctx.tdev))
         return ev
