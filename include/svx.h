@@ -336,6 +336,64 @@ int svx_align_batch(svx_ctx *ctx, const svx_align_params *params, const svx_pair
 int svx_alignment_rows(svx_ctx *ctx, int dtype, int d, const svx_pair *pairs, int n_pairs, double max_score, int64_t cap,
                        void *x_rows, void *y_rows, void *x_unit, void *y_unit, int unit_dtype, int32_t *src, int64_t *count);
 
+/* ---- margin rows for concatenated alignments: the post-filter chain on the device ---------------------------
+ * Between alignment and margin scoring the reference runs filter_by_cost --max_cost, concat_aligns and filter_by_dur
+ * (example/voxpopuli/run.sh steps 6.1, 6.3, 6.4; the audio-based filter_untrans_align of 6.2 is NOT part of this entry).
+ * concat_aligns only joins alignments that are directly connected on both sides, so a joined alignment is a contiguous run
+ * of segments on each side, and while that run is at most k0 x k1 segments its embedding is the candidate row
+ * vecs0[x_len-1][x_start+x_len-1] as for svx_alignment_rows.  svx_concat_rows applies the chain to the alignment rows of a
+ * batch and gathers the rows of every output that fits (csrc/svx_concatrows.hip).
+ *
+ * pairs: as svx_alignment_rows reads them.  frames (HOST array of n_pairs): per pair the device arrays [n][2] and [m][2] of
+ * (start, end) sample positions of the segments (svecalign/utils/file_utils.py read_segments); may be NULL only when
+ * max_num_align == 1 and min_frames <= 0, and is then not read.
+ *
+ * BASE ROWS (filter_by_cost.py:39-87).  Row r of pair p is a base row iff  info[1] == 0 and 0 <= r < min(info[0], n+m+2);
+ * x_len >= 1 and y_len >= 1;  0 <= x_start, x_start + x_len <= n, 0 <= y_start, y_start + y_len <= m;  scores[r] <=
+ * max_score as a plain double comparison (NaN fails).  There is no width limit.  A row that is not a base row is never used
+ * to form an address.  c_0 < c_1 < ... are the base rows of the pair.
+ *
+ * JOINING (concat_aligns.py:56-110).  For every i the output e = 0 is c_i alone; outputs e = 1 .. max_num_align-1 follow
+ * while c_{i+e} exists IN THE SAME PAIR and passes, against the run so far (first row f = c_i, last row l = c_{i+e-1}, with
+ * xs/xl/ys/yl the row's fields, xend = xs + xl - 1, F0 / F1 the frames of the two sides), in this order:
+ *   (double)(F0[xend(nx)][1] - F0[xs(f)][0]) / sample_rate <= max_dur;  if both_sides, the same with F1 / y;
+ *   xs(nx) == xs(l) + xl(l) and ys(nx) == ys(l) + yl(l);
+ *   (double)(F0[xs(nx)][0] - F0[xend(l)][1]) / sample_rate <= max_sil, and the same with F1 / y.
+ * The first failure ends the run of that i.  Differences are taken in int64, divisions in double.
+ * The span of (i, e): x_start = xs(c_i), x_len = xs(c_{i+e}) + xl(c_{i+e}) - xs(c_i); likewise y.
+ *
+ * DURATION FILTER (filter_by_dur.py:62-63), when min_frames > 0: an output is dropped unless
+ * min_frames <= F0[x_start+x_len-1][1] - F0[x_start][0] and the same on the target side.
+ *
+ * FIT.  An output that passes is numbered and gathered only if x_len <= k0 and y_len <= k1; otherwise it is counted in
+ * counts[1] ("wide": the reference embeds it with the encoder) and nothing is written for it.
+ *
+ * Fitting outputs are numbered j = 0, 1, ... in (pair, i, e) ascending order, the line order of the reference's files.  At j:
+ *   x_rows[j], y_rows[j], x_unit[j], y_unit[j]: what svx_alignment_rows defines for a row with that span;
+ *   meta[j] = (p, c_i, c_{i+e}, e + 1, x_start, x_len, y_start, y_len)              ([cap][8] int32).
+ * counts (device, [2]): counts[0] = the number of fitting outputs, also when it exceeds cap, counts[1] = the wide ones.  Only
+ * j < cap is written and nothing else of the output buffers is touched.  cap = 0 or n_pairs = 0 is legal.
+ * d, alignment, dtypes, null arguments: the rules of svx_alignment_rows; max_num_align outside 1 .. SVX_CONCAT_MAX, a
+ * non-positive sample_rate or NaN limits where frames are needed, and missing frames return SVX_ERR_ARG with text and queue
+ * nothing.  Asynchronous on the context's stream, no host synchronisation, svx_flush first.  Seven launches (count, scan
+ * and write of the base rows; count, scan and write of the outputs; gather) with no host round trip in between.  Scratch
+ * is the grow-only buffer of svx_alignment_rows (here also the compacted base rows, 24 bytes per alignment row, and 16 bytes
+ * per output up to cap), counted in svx_scratch_bytes, uploaded through the same pinned staging. */
+#define SVX_CONCAT_MAX 8
+typedef struct svx_frames { const int32_t *src, *tgt; } svx_frames;
+typedef struct svx_concat_params {
+    double  max_score;        /* cost filter, as svx_alignment_rows' max_score */
+    int32_t max_num_align;    /* 1 .. SVX_CONCAT_MAX; 1 = no joining */
+    int32_t sample_rate;      /* > 0 (16000) */
+    double  max_sil, max_dur; /* seconds */
+    int32_t both_sides;       /* apply max_dur to the target span too */
+    int32_t pad;
+    int64_t min_frames;       /* duration filter; <= 0 keeps everything */
+} svx_concat_params;
+int svx_concat_rows(svx_ctx *ctx, int dtype, int d, const svx_pair *pairs, const svx_frames *frames, int n_pairs,
+                    const svx_concat_params *params, int64_t cap, void *x_rows, void *y_rows, void *x_unit, void *y_unit,
+                    int unit_dtype, int32_t *meta, int64_t *counts);
+
 /* Per-level intermediates of the LAST svx_align_batch call on this context -- the entries of the `stack` the reference
  * returns (dp_utils.py:412-537) -- as device pointers into the context's scratch arena (valid until the next call;
  * the scalar fields are read back, which synchronises the stream).  Pointers are NULL for what a level does not have

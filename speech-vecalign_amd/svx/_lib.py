@@ -65,6 +65,24 @@ class Pair(ctypes.Structure):
     ]
 
 
+class Frames(ctypes.Structure):
+    """svx_frames: per pair the device arrays [n][2], [m][2] of (start, end) sample positions."""
+    _fields_ = [("src", c_vp), ("tgt", c_vp)]
+
+
+class ConcatParams(ctypes.Structure):
+    """svx_concat_params (include/svx.h)."""
+    _fields_ = [
+        ("max_score", ctypes.c_double),
+        ("max_num_align", ctypes.c_int32), ("sample_rate", ctypes.c_int32),
+        ("max_sil", ctypes.c_double), ("max_dur", ctypes.c_double),
+        ("both_sides", ctypes.c_int32), ("pad", ctypes.c_int32),
+        ("min_frames", ctypes.c_int64),
+    ]
+
+
+SVX_CONCAT_MAX = 8
+
 _SIGS = {
     "svx_create": (c_int, [c_int, ctypes.POINTER(c_vp)]),
     "svx_destroy": (c_int, [c_vp]),
@@ -108,6 +126,8 @@ _SIGS = {
     "svx_knob_count": (c_i64, [c_int, c_int, c_int]),
     "svx_align_batch": (c_int, [c_vp, ctypes.POINTER(AlignParams), ctypes.POINTER(Pair), c_int]),
     "svx_alignment_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), c_int, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
+    "svx_concat_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), ctypes.POINTER(Frames), c_int, ctypes.POINTER(ConcatParams), c_i64,
+                                c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "svx_debug_level": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(LevelView)]),
     "svx_copy_to_host": (c_int, [c_vp, c_vp, c_vp, c_i64]),
     "svx_set_profiling": (c_int, [c_vp, c_int]),

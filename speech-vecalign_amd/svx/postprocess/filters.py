@@ -5,6 +5,7 @@ Same behaviour, file formats and defaults as the reference scripts:
   concat_consecutive  svecalign/postprocess/concat_aligns.py:56-110   (runs of up to `max_num_align` connected
                                                                         alignments, silence and duration limits)
   keep_by_duration    svecalign/postprocess/filter_by_dur.py:43-71    (both sides at least `min_frames` long)
+  post_chain          the three composed in memory (seg_align.align --post_dir; svx_concat_rows does the same on the device)
   cost_limit          the double threshold that keeps what keep_by_cost keeps from the '%.6f' text (svx_alignment_rows)
 Each has the reference's command line in its own module (filter_by_cost.py, concat_aligns.py, filter_by_dur.py).
 """
@@ -104,6 +105,20 @@ def keep_by_duration(align_path: Path, src_seg_path: Path, tgt_seg_path: Path, m
     else:
         logger.info(f"Skip {Path(out_path).as_posix()}. You can double check inputs {Path(align_path).as_posix()}")
     return len(kept)
+
+
+def post_chain(rows_with_scores: Iterable[Tuple[Sequence[int], Sequence[int], float]], src_frames: Sequence[Tuple[int, int]],
+               tgt_frames: Sequence[Tuple[int, int]], max_cost: Optional[float], max_num_align: int, max_sil: float, max_dur: float,
+               both_sides: bool, min_frames: int) -> List[Alignment]:
+    """keep_by_cost(max_cost) -> concat_consecutive -> keep_by_duration on (src ids, tgt ids, cost) rows, without the files in
+    between: what filter_by_cost --max_cost, concat_aligns and filter_by_dur leave of the alignment file written from these
+    rows.  The cost is compared as the file holds it, i.e. after the '%.6f' text round trip; max_cost None only drops the
+    deletions."""
+    kept = [(list(s), list(t)) for s, t, c in rows_with_scores
+            if len(s) and len(t) and not (max_cost is not None and float("%.6f" % c) > max_cost)]
+    joined = concat_consecutive(kept, src_frames, tgt_frames, max_num_align, max_sil, max_dur, SAMPLE_RATE, both_sides)
+    return [(s, t) for s, t in joined
+            if min_frames <= src_frames[s[-1]][1] - src_frames[s[0]][0] and min_frames <= tgt_frames[t[-1]][1] - tgt_frames[t[0]][0]]
 
 
 def for_each_pair(metadata: str, src_lang: str, tgt_lang: str, align_dir: str, out_dir: str,

@@ -17,6 +17,14 @@ the reference's second pass of the speech encoder (postprocess/embed_align.py): 
 alignment's span is the candidate row the DP has just read, so after every batch svx_alignment_rows gathers those rows
 on the device, and after the last batch they are scored against the union over ranks (global_margin_scores).  Under
 torch.distributed.run the ranks form a process group for that exchange; the alignment files do not change.
+
+--concat_max_num N / --min_dur S (with --max_sil, --concat_max_dur, --apply_dur_cond_to_both_sides) put the reference's text
+post-filters between alignment and margin scoring -- filter_by_cost --max_cost, concat_aligns --max_num_align N, filter_by_dur
+--min_dur S (example/voxpopuli/run.sh steps 6.1, 6.3, 6.4) -- into this job.  The audio-based filter_untrans_align of step 6.2
+is NOT part of the chain.  With --margin_dir the chain runs on the device (svx_concat_rows) and the margin files hold one
+line per joined alignment whose span is still a candidate row (at most k0 x k1 segments); wider ones need the encoder and
+are only counted.  --post_dir DIR writes the chain's full output, wide lines included, as concat_aligns / filter_by_dur write
+it; that is host work on the results already fetched (filters.post_chain).
 """
 import argparse
 import dataclasses
@@ -78,12 +86,45 @@ def parse_args(argv=None):
     p.add_argument("--margin_storage", choices=["fp16", "bf16"], default="fp16", help="--margin_dir: storage of the unit-norm database rows")
     p.add_argument("--margin_exchange", choices=["allgather", "ring"], default="allgather",
                    help="--margin_dir: how the ranks' rows meet (global_margin_scores)")
+    p.add_argument("--concat_max_num", type=int, default=None,
+                   help="join up to N consecutive connected alignments (concat_aligns --max_num_align N) before --margin_dir / --post_dir")
+    p.add_argument("--max_sil", type=float, default=1.0, help="--concat_max_num: largest gap between joined alignments, seconds (concat_aligns --max_sil)")
+    p.add_argument("--concat_max_dur", type=float, default=20.0, help="--concat_max_num: longest joined source span, seconds (concat_aligns --max_dur)")
+    p.add_argument("--apply_dur_cond_to_both_sides", action="store_true", default=False, help="--concat_max_num: --concat_max_dur also limits the target span")
+    p.add_argument("--min_dur", type=float, default=None,
+                   help="drop (joined) alignments with a side shorter than S seconds (filter_by_dur --min_dur S) before --margin_dir / --post_dir")
+    p.add_argument("--post_dir", type=str, default=None,
+                   help="also write {post_dir}/{src}-{tgt}/{s}-{t}.txt: the alignments after filter_by_cost --max_cost, concat_aligns and "
+                        "filter_by_dur, one src_ids:tgt_ids per line (the audio filter filter_untrans_align is not part of this chain)")
     args = p.parse_args(argv)
+    if args.concat_max_num is not None and not 1 <= args.concat_max_num <= 8:
+        p.error("--concat_max_num must be 1 .. 8")
+    if args.min_dur is not None and args.min_dur < 0:
+        p.error("--min_dur must be >= 0")
+    if post_chain_wanted(args):
+        if args.margin_dir is None and args.post_dir is None:
+            p.error("--concat_max_num / --min_dur need --margin_dir or --post_dir")
+    if args.post_dir is not None and args.skip_existing:
+        p.error("--post_dir cannot be combined with --skip_existing")
     if args.margin_dir is not None and args.skip_existing:
         p.error("--margin_dir needs the rows of every pair: it cannot be combined with --skip_existing")
     if args.max_cost is not None and args.max_cost < 0:
         p.error("--max_cost must be >= 0")
     return args
+
+
+def post_chain_wanted(args) -> bool:
+    """Whether the post-filter chain (cost, joining, duration) runs, and with it the reading of the segment timestamps."""
+    return any(getattr(args, k, None) is not None for k in ("concat_max_num", "min_dur", "post_dir"))
+
+
+def post_chain_params(args) -> dict:
+    """The chain's parameters as filters.post_chain / PreparedBatch.concat_rows take them (without the cost threshold)."""
+    from ..postprocess.filters import SAMPLE_RATE
+    return dict(max_num_align=1 if getattr(args, "concat_max_num", None) is None else args.concat_max_num,
+                max_sil=getattr(args, "max_sil", 1.0), max_dur=getattr(args, "concat_max_dur", 20.0),
+                both_sides=bool(getattr(args, "apply_dur_cond_to_both_sides", False)),
+                min_frames=0 if getattr(args, "min_dur", None) is None else int(SAMPLE_RATE * args.min_dur))   # filter_by_dur.py:23
 
 
 @dataclasses.dataclass
@@ -161,6 +202,15 @@ def _write_result(path: str, rows: np.ndarray, scores: np.ndarray):
     Path(tmp).replace(path)
 
 
+def _write_post(path: str, rows: np.ndarray, scores: np.ndarray, frames, max_cost, chain: dict):
+    """--post_dir: the chain's output for one pair, as concat_aligns / filter_by_dur write it; like them, no file when nothing is left."""
+    from ..postprocess.filters import post_chain
+    from ..vecalign.dp_utils import rows_to_alignments
+    out = post_chain([(s, t, c) for (s, t), c in zip(rows_to_alignments(rows), scores.tolist())], frames[0], frames[1], max_cost, **chain)
+    if out:
+        _write_text(path, "".join(f"{s}:{t}\n" for s, t in out))
+
+
 def _write_text(path: str, text: str):
     tmp = path + ".tmp"
     with open(tmp, "w") as fp:
@@ -175,27 +225,38 @@ class MarginRows:
         from ..postprocess.filters import cost_limit
         self.args = args
         self.limit = float("inf") if args.max_cost is None else cost_limit(args.max_cost)
+        self.chain = dict(post_chain_params(args), max_score=self.limit) if post_chain_wanted(args) else None
+        self.n_fit = self.n_wide = 0
         self.parts = []    # per batch: (x_rows, y_rows, x_unit, y_unit) trimmed to the kept rows
         self.files = []    # per pair with kept rows, in row order: (file name, ["src_ids:tgt_ids", ...])
         self.d = self.dtype = None
 
     def gather(self, pb):
         """Behind pb.run() on the compute stream (asynchronous)."""
-        pb.alignment_rows(self.limit, self.args.margin_storage)
+        if self.chain is not None:
+            pb.concat_rows(self.chain, self.args.margin_storage)
+        else:
+            pb.alignment_rows(self.limit, self.args.margin_storage)
 
     def collect(self, chunk, pb, info, align, offs):
         """After the batch's fetch event: trim the row buffers to the count and note the ids of the kept alignments."""
         cnt = pb.rows_count()
+        if self.chain is not None:
+            self.n_fit += cnt
+            self.n_wide += int(pb.h_rows[0][1])
         x_rows, y_rows, x_unit, y_unit, _, _ = pb.rows
         self.d, self.dtype = int(x_rows.shape[1]), x_rows.dtype
         pb.rows = None
         if cnt == 0:
             return
         self.parts.append(tuple(t[:cnt].clone() for t in (x_rows, y_rows, x_unit, y_unit)))
-        src = pb.h_rows[1].numpy()[:cnt]
+        src = pb.h_rows[1].numpy()[:cnt]   # (pair, row) per kept alignment, or svx_concat_rows' meta
         bounds = np.searchsorted(src[:, 0], np.arange(len(chunk) + 1))
         for i, p in enumerate(chunk):
-            rows = align[int(offs[i]) + src[bounds[i]:bounds[i + 1], 1]]
+            if self.chain is not None:
+                rows = src[bounds[i]:bounds[i + 1], 4:8]
+            else:
+                rows = align[int(offs[i]) + src[bounds[i]:bounds[i + 1], 1]]
             if len(rows):
                 self.files.append((os.path.basename(p.output_path),
                                    ["%s:%s" % (list(range(r[0], r[0] + r[1])), list(range(r[2], r[2] + r[3]))) for r in rows.tolist()]))
@@ -205,6 +266,9 @@ class MarginRows:
         import torch
         from ..postprocess.score_align import _dist_rank_world, global_margin_scores
         a = self.args
+        if self.chain is not None:
+            logger.info(f"post-filter chain: {self.n_fit} joined alignments fit a candidate row and are margin-scored, "
+                        f"{self.n_wide} are wider (they need the encoder and are left out of {a.margin_dir})")
         _, world, _ = _dist_rank_world()
         udt = torch.float16 if a.margin_storage == "fp16" else torch.bfloat16
         if world > 1:   # a rank without pairs still takes part in the exchange: it needs the others' row shape
@@ -241,7 +305,14 @@ def _prepare_pair(p: VecalignData, args, src_k: int, tgt_k: int):
     tt, _ = candidate_table_from_files(p.tgt_seg_path, p.tgt_concat_path, tgt_k, p.tgt_ignore_indices)
     se = read_embeddings_pinned(p.src_embed_path, args.is_stopes_embed, args.fp16_embed)
     te = read_embeddings_pinned(p.tgt_embed_path, args.is_stopes_embed, args.fp16_embed)
-    return st, tt, se, te
+    fr = None
+    if post_chain_wanted(args):   # (start, end) sample positions per segment, for joining and the duration filter
+        from ..utils.file_utils import read_segments
+        fr = tuple(np.asarray(read_segments(path), dtype=np.int64).reshape(-1, 2) for path in (p.src_seg_path, p.tgt_seg_path))
+        for f in fr:
+            if len(f) and (f.min() < -2 ** 31 or f.max() >= 2 ** 31):
+                raise ValueError(f"{p.src_seg_path}: sample positions beyond int32")
+    return st, tt, se, te, fr
 
 
 def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Optional[int] = None, stats: Optional[dict] = None):
@@ -261,6 +332,11 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
     types, src_k, tgt_k, width_over2 = resolve_search_params(args.alignment_max_size, None, args.search_buffer_size)
     todo = [p for p in pairs if not (args.skip_existing and Path(p.output_path).exists())]
     margin = MarginRows(args) if getattr(args, "margin_dir", None) is not None else None
+    chain = post_chain_params(args) if post_chain_wanted(args) else None
+    post_dir = None
+    if getattr(args, "post_dir", None) is not None:
+        post_dir = Path(args.post_dir) / f"{args.src_lang}-{args.tgt_lang}"
+        post_dir.mkdir(parents=True, exist_ok=True)
     if not todo:
         if margin is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:   # the other ranks wait for this one in the exchange
             margin.finish(_lib.context())
@@ -295,6 +371,9 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
         for i, p in enumerate(chunk):
             o, cnt = int(offs[i]), int(info[i, 0])
             writes.append(out_pool.apply_async(_write_result, (p.output_path, align[o:o + cnt], scores[o:o + cnt])))
+            if post_dir is not None:
+                writes.append(out_pool.apply_async(_write_post, ((post_dir / os.path.basename(p.output_path)).as_posix(), align[o:o + cnt],
+                                                                 scores[o:o + cnt], held[0][i][4], args.max_cost, chain)))
         return writes, (pb, held)  # (the pinned result buffers stay alive until the writers are done)
 
     pending_job, pending_writes = None, deque()
@@ -308,12 +387,12 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
             # ---- uploads on the copy stream (pinned -> device), then gather + align on the compute stream
             with torch.cuda.stream(copy_stream):
                 dev_in = [(torch.from_numpy(st).to(dev, non_blocking=True), torch.from_numpy(tt).to(dev, non_blocking=True),
-                           se.to(dev, non_blocking=True), te.to(dev, non_blocking=True)) for st, tt, se, te in prepared]
+                           se.to(dev, non_blocking=True), te.to(dev, non_blocking=True)) for st, tt, se, te, _ in prepared]
                 up = torch.cuda.Event()
                 up.record(copy_stream)
             compute.wait_event(up)
             docs = []
-            for (st, tt, se, te), (dst, dtt, dse, dte) in zip(prepared, dev_in):
+            for (st, tt, se, te, _), (dst, dtt, dse, dte) in zip(prepared, dev_in):
                 for x in (dst, dtt, dse, dte):
                     x.record_stream(compute)
                 sv, tv = gather_candidates(dse, dst), gather_candidates(dte, dtt)
@@ -329,7 +408,8 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
             else:  # dense: the band covers the lattice (width_over2 > max(N, M))
                 w2, search = max(max(int(sv.shape[1]), int(tv.shape[1])) for sv, tv in docs) + 1, "straight"
             pb = PreparedBatch(docs, types, args.del_percentile_frac, w2, args.max_size_full_dp,
-                               args.costs_sample_size, args.num_samps_for_norm, rngs=rngs, search=search)
+                               args.costs_sample_size, args.num_samps_for_norm, rngs=rngs, search=search,
+                               frames=[q[4] for q in prepared] if margin is not None and chain is not None else None)
             pb.run()
             if margin is not None:
                 margin.gather(pb)

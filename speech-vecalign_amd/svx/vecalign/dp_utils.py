@@ -159,8 +159,10 @@ class PreparedBatch:
     is built here once."""
 
     def __init__(self, pairs, final_alignment_types, del_percentile_frac, width_over2, max_size_full_dp,
-                 costs_sample_size, num_samps_for_norm, rngs=None, norms=None, device=None, search="coarse_to_fine"):
-        """search: "coarse_to_fine" (the reference's recursion) or "straight" (band of half-width `width_over2`
+                 costs_sample_size, num_samps_for_norm, rngs=None, norms=None, device=None, search="coarse_to_fine", frames=None):
+        """frames: per pair (src, tgt) segment timestamps, [n, 2] and [m, 2] (start, end) sample positions (read_segments);
+        kept on the device as int32 for concat_rows().
+        search: "coarse_to_fine" (the reference's recursion) or "straight" (band of half-width `width_over2`
         around the straight line from (0,0) to (N,M): Sakoe-Chiba / dense search, include/svx.h SVX_SEARCH_STRAIGHT;
         no pyramid, so `max_size_full_dp` is ignored)."""
         if search not in ("coarse_to_fine", "straight"):
@@ -186,6 +188,21 @@ class PreparedBatch:
             if a.dim() != 3 or b.dim() != 3:
                 raise ValueError("Buffer has wrong number of dimensions (expected 3, got %d)" % a.dim())
             assert a.shape[2] == b.shape[2]
+        self.frames = self.cframes = None
+        if frames is not None:
+            if len(frames) != len(self.vecs):
+                raise ValueError("frames: one (src, tgt) pair of timestamp arrays per document pair")
+            self.frames = []
+            self.cframes = (_lib.Frames * len(self.vecs))()
+            for i, ((a, b), fr) in enumerate(zip(self.vecs, frames)):
+                dev = []
+                for v, f in zip((a, b), fr):
+                    f = t.as_tensor(np.asarray(f).reshape(-1, 2) if not t.is_tensor(f) else f)
+                    if tuple(f.shape) != (int(v.shape[1]), 2):
+                        raise ValueError("frames of pair %d: shape %s for %d segments" % (i, tuple(f.shape), int(v.shape[1])))
+                    dev.append(f.to(device=ctx.tdev, dtype=t.int32).contiguous())
+                self.frames.append(tuple(dev))
+                self.cframes[i].src, self.cframes[i].tgt = dev[0].data_ptr(), dev[1].data_ptr()
         prm.dtype = dts.pop()
         prm.d = int(self.vecs[0][0].shape[2])
         prm.n_types = len(self.types)
@@ -310,19 +327,65 @@ class PreparedBatch:
         self.rows = (x_rows, y_rows, x_unit, y_unit, src, count)
         return self.rows
 
+    def concat_rows(self, params, unit_storage="fp16"):
+        """alignment_rows() behind the reference's post-filter chain filter_by_cost -> concat_aligns -> filter_by_dur
+        (svx_concat_rows, include/svx.h): the candidate rows of every joined alignment that fits a candidate.
+        params: dict(max_score, max_num_align, max_sil, max_dur, both_sides, min_frames, sample_rate) -- missing keys take
+        (inf, 1, 1.0, 20.0, False, 0, 16000) -- or a _lib.ConcatParams.  Joining and the duration filter need the batch's
+        `frames`.  -> device tensors (x_rows, y_rows, x_unit, y_unit as alignment_rows(), meta [cap, 8] int32 = (pair, first
+        row, last row, rows joined, x_start, x_len, y_start, y_len), counts [2] int64 = (fitting rows, wide rows)).
+        cap = max_num_align * sum over pairs of min(n, m).  rows_count() and fetch_async() work as after alignment_rows()
+        (h_rows = (counts, meta))."""
+        if unit_storage not in ("fp16", "bf16", None):
+            raise ValueError(f"unit_storage {unit_storage!r}: 'fp16', 'bf16' or None")
+        ctx = self.ctx
+        t = ctx.torch
+        ctx.use_current_stream()
+        if isinstance(params, _lib.ConcatParams):
+            prm = params
+        else:
+            unknown = set(params) - {"max_score", "max_num_align", "max_sil", "max_dur", "both_sides", "min_frames", "sample_rate"}
+            if unknown:
+                raise ValueError("concat_rows: unknown parameters %s" % sorted(unknown))
+            prm = _lib.ConcatParams()
+            prm.max_score = float(params.get("max_score", float("inf")))
+            prm.max_num_align = int(params.get("max_num_align", 1))
+            prm.sample_rate = int(params.get("sample_rate", 16000))
+            prm.max_sil = float(params.get("max_sil", 1.0))
+            prm.max_dur = float(params.get("max_dur", 20.0))
+            prm.both_sides = 1 if params.get("both_sides", False) else 0
+            prm.min_frames = int(params.get("min_frames", 0))
+        cap = max(1, int(prm.max_num_align)) * int(sum(min(int(a.shape[1]), int(b.shape[1])) for a, b in self.vecs))
+        d, dt = int(self.prm.d), self.vecs[0][0].dtype
+        x_rows = t.empty((cap, d), dtype=dt, device=ctx.tdev)
+        y_rows = t.empty((cap, d), dtype=dt, device=ctx.tdev)
+        x_unit = y_unit = None
+        code = _lib.SVX_F16
+        if unit_storage is not None:
+            udt, code = (t.float16, _lib.SVX_F16) if unit_storage == "fp16" else (t.bfloat16, _lib.SVX_BF16)
+            x_unit = t.empty((cap, d), dtype=udt, device=ctx.tdev)
+            y_unit = t.empty((cap, d), dtype=udt, device=ctx.tdev)
+        meta = t.empty((cap, 8), dtype=t.int32, device=ctx.tdev)
+        counts = t.empty((2,), dtype=t.int64, device=ctx.tdev)
+        ctx.check(ctx.lib.svx_concat_rows(ctx.h, int(self.prm.dtype), d, self.cpairs, self.cframes, len(self.vecs), ctypes.byref(prm), cap,
+                                          _p(x_rows), _p(y_rows), _p(x_unit), _p(y_unit), code, _p(meta), _p(counts)))
+        self.rows = (x_rows, y_rows, x_unit, y_unit, meta, counts)
+        return self.rows
+
     def rows_count(self):
-        """Number of rows alignment_rows() kept.  Uses the copy of fetch_async() when there is one (after its event);
+        """Number of rows alignment_rows() / concat_rows() kept.  Uses the copy of fetch_async() when there is one (after its event);
         otherwise this read synchronises the stream."""
         if getattr(self, "h_rows", None) is not None:
             return int(self.h_rows[0][0])
         if getattr(self, "rows", None) is None:
             raise RuntimeError("rows_count() before alignment_rows()")
-        return int(self.rows[5].item())
+        return int(self.rows[5][0].item())
 
     def fetch_async(self):
         """Queue the device -> pinned-host copies of the outputs behind run() on the current stream and return
         an event that fires when they have landed (the host pipeline formats batch i while batch i+1 computes).
-        After alignment_rows() its `count` and `src` travel along (h_rows = (count, src))."""
+        After alignment_rows() its `count` and `src` travel along (h_rows = (count, src)); after concat_rows() its `counts`
+        and `meta`."""
         t = self.ctx.torch
         self.ctx.flush()  # (a no-op unless the pipeline is on)
         self.h_out = tuple(t.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in (self.info, self.align, self.scores, self.del_pen))
