@@ -205,6 +205,24 @@ int svx_knn_topk_merge(svx_ctx *ctx, const void *queries, int q_dtype, int64_t n
 int svx_knn_search(svx_ctx *ctx, const void *queries, int q_dtype, int64_t n, const void *db, int db_dtype,
                    int64_t n_db, int d, int k, int64_t id_base, float *sims, int64_t *ids, int first);
 
+/* The same search over GROUPS: query rows [q_off[g], q_off[g+1]) search database rows [db_off[g], db_off[g+1]) and nothing
+ * else, for g < n_groups, in one launch (csrc/svx_groupsearch.hip) -- the two documents of every parallel pair of a corpus
+ * (Local Mining), or any "neighbours from the same document only" normalisation.  q_off, db_off: HOST arrays of
+ * n_groups + 1 entries that start at 0 and never decrease; they are copied before the call returns and may be freed then.
+ * queries [n][d] with n = q_off[n_groups]; db holds at least db_off[n_groups] rows.
+ * sims [n][k] float32, ids [n][k] int64 = GLOBAL database row numbers (db_off[g] + the row inside the group).  For the rows
+ * of group g the result is, bit for bit in values and ids, what
+ *   svx_knn_search(queries + q_off[g] * d, n_g, db + db_off[g] * d, N_g, d, k, id_base = db_off[g], ..., first = 1)
+ * writes on the same build: the same total order, the same tie rule, trailing (-inf, -1) entries where the group has fewer
+ * than k database rows.  Empty groups are legal on either side, and so is n_groups = 0.  There is no continuation mode.
+ * d, k, the dtypes and finite rows: the rules of svx_knn_search.  A violation, a null argument, an offset array that does not
+ * start at 0 or decreases, a negative n_groups, or offsets that need 2^31 or more workgroups (a group of n_g queries takes
+ * ceil(n_g / 64)) return SVX_ERR_ARG with text and queue nothing.  Asynchronous on the context's stream, no host
+ * synchronisation.  Scratch (the two offset arrays and 8 bytes per workgroup) lives in the grow-only buffer of
+ * svx_alignment_rows, counted in svx_scratch_bytes, and is uploaded through the same pinned staging. */
+int svx_knn_search_groups(svx_ctx *ctx, const void *queries, int q_dtype, const void *db, int db_dtype, int d, int k,
+                          const int64_t *q_off, const int64_t *db_off, int n_groups, float *sims, int64_t *ids);
+
 /* score_align.py:151-160: scores[i] = <x_i/|x_i|, y_i/|y_i|> / ((mean_xy[i] + mean_yx[i]) / 2)
  * (SVX_MARGIN_RATIO) or minus it (SVX_MARGIN_DISTANCE).  x, y [n][d] of `dtype`. */
 int svx_margin_scores(svx_ctx *ctx, const void *x, const void *y, int dtype, int64_t n, int d, const float *mean_xy,

@@ -110,6 +110,7 @@ _SIGS = {
     "svx_knn_mean_sim": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_int, c_vp]),
     "svx_knn_topk_merge": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_int, c_vp]),
     "svx_knn_search": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_i64, c_int, c_int, c_i64, c_vp, c_vp, c_int]),
+    "svx_knn_search_groups": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "svx_margin_scores": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_int, c_vp]),
     "svx_knn_list_means": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),
     "svx_margin_candidates": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp]),

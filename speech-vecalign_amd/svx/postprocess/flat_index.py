@@ -191,6 +191,54 @@ class FlatIndex:
         sims, ids = self.merge_search(queries, k)
         return (2.0 - 2.0 * sims if l2 else sims), ids
 
+    # -- grouped search: every block of queries sees only its own range of rows (Local Mining: one document pair per group)
+    def search_groups(self, queries, k: int, q_off, db_off):
+        """One exact search per group in a single launch (svx_knn_search_groups): query rows [q_off[g], q_off[g+1]) are
+        searched in this index's rows [db_off[g], db_off[g+1]) and nowhere else.  q_off, db_off: host integer sequences of
+        n_groups + 1 entries starting at 0 and never decreasing, q_off[-1] = the number of queries, db_off[-1] <= ntotal.
+        -> (sims float32 [n, k], ids int64 [n, k]) device tensors; the ids are row numbers of this index, and the rows of
+        group g equal, bit for bit, `search` of the group's queries in an index of the group's rows, plus db_off[g]."""
+        ctx = self.ctx
+        t = ctx.torch
+        q = to_device_rows(ctx, queries)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"expected [n, {self.d}] queries, got {tuple(q.shape)}")
+        offs = []
+        for name, a in (("q_off", q_off), ("db_off", db_off)):
+            a = np.asarray(a)
+            if a.ndim != 1 or a.shape[0] < 1 or a.dtype.kind not in "iu":
+                raise ValueError(f"{name} must be a vector of n_groups + 1 integers")
+            offs.append(np.ascontiguousarray(a, dtype=np.int64))
+        q_off, db_off = offs
+        if q_off.shape != db_off.shape:
+            raise ValueError(f"q_off has {q_off.shape[0]} entries, db_off {db_off.shape[0]}")
+        if int(q_off[-1]) != q.shape[0]:
+            raise ValueError(f"q_off ends at {int(q_off[-1])} for {q.shape[0]} queries")
+        db = self.rows
+        if int(db_off[-1]) > db.shape[0]:
+            raise ValueError(f"db_off ends at {int(db_off[-1])}, the index holds {db.shape[0]} rows")
+        shape = (q.shape[0], int(k))
+        sims = t.empty(shape, dtype=t.float32, device=ctx.tdev)
+        ids = t.empty(shape, dtype=t.int64, device=ctx.tdev)
+        ctx.check(ctx.lib.svx_knn_search_groups(ctx.h, ctypes.c_void_p(q.data_ptr() if q.shape[0] else None), _torch_dtype_code(t, q.dtype),
+                                                ctypes.c_void_p(db.data_ptr() if db.shape[0] else None), self.code, self.d, int(k),
+                                                ctypes.c_void_p(q_off.ctypes.data), ctypes.c_void_p(db_off.ctypes.data),
+                                                int(q_off.shape[0]) - 1, ctypes.c_void_p(sims.data_ptr() if q.shape[0] else None),
+                                                ctypes.c_void_p(ids.data_ptr() if q.shape[0] else None)))
+        return sims, ids
+
+    @classmethod
+    def over(cls, unit_rows, device=None) -> "FlatIndex":
+        """An index over a contiguous fp16 / bf16 device tensor [n, d] of unit rows as it stands, without a copy."""
+        import torch as t
+        if not hasattr(unit_rows, "data_ptr") or unit_rows.ndim != 2 or unit_rows.dtype not in (t.float16, t.bfloat16) \
+                or not unit_rows.is_cuda or not unit_rows.is_contiguous():
+            raise ValueError("unit rows must be a contiguous fp16 or bf16 [n, d] device tensor")
+        idx = cls(d=int(unit_rows.shape[1]), storage="fp16" if unit_rows.dtype == t.float16 else "bf16",
+                  device=unit_rows.device.index if device is None else device)
+        idx._rows = unit_rows
+        return idx
+
     # -- files
     @classmethod
     def read(cls, path, storage: str = "fp16", device=None) -> "FlatIndex":

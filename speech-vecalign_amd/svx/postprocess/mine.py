@@ -14,7 +14,10 @@ kept (svx_margin_candidates); the retrieval step then selects pairs:
                   greedy pass that keeps a pair when neither of its rows was kept before (svx_mine_greedy)
 
 Rows without a valid neighbour (best id -1) are dropped before the sort; `threshold` keeps score > threshold and is
-applied after the selection, as in LASER.  Output lines: score<TAB>source row<TAB>target row."""
+applied after the selection, as in LASER.  Output lines: score<TAB>source row<TAB>target row.
+
+Local mining -- the same inside every parallel document pair, the paper's second baseline -- is `mine_local` (all pairs of
+a batch at once: one grouped search per direction, `FlatIndex.search_groups`); its CLI is svx.postprocess.mine_local."""
 import argparse
 import ctypes
 import logging
@@ -164,6 +167,90 @@ def mine_bitexts(idx_x: FlatIndex, idx_y: FlatIndex, k: int = 16, margin: str = 
     if retrieval not in RETRIEVALS:
         raise ValueError(f"retrieval {retrieval!r}: one of {', '.join(RETRIEVALS)}")
     return select_pairs(*best_candidates(idx_x, idx_y, k, margin), retrieval=retrieval, threshold=threshold)
+
+
+# ------------------------------------------------------------------------------------------------ local mining
+def _group_offsets(x_off, y_off):
+    offs = []
+    for name, a in (("x_off", x_off), ("y_off", y_off)):
+        a = np.asarray(a)
+        if a.ndim != 1 or a.shape[0] < 1 or a.dtype.kind not in "iu":
+            raise ValueError(f"{name} must be a vector of n_groups + 1 integers")
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if a[0] != 0 or (np.diff(a) < 0).any():
+            raise ValueError(f"{name} must start at 0 and never decrease")
+        offs.append(a)
+    if offs[0].shape != offs[1].shape:
+        raise ValueError(f"x_off has {offs[0].shape[0]} entries, y_off {offs[1].shape[0]}")
+    return offs
+
+
+def small_groups(x_off, y_off, k: int) -> np.ndarray:
+    """bool [n_groups]: the pairs with fewer than k rows on either side, which local mining leaves out."""
+    x_off, y_off = _group_offsets(x_off, y_off)
+    return (np.diff(x_off) < k) | (np.diff(y_off) < k)
+
+
+def _pack_groups(rows, off, kept):
+    """The rows of the groups `kept`, packed -> (rows, their offsets)."""
+    import torch as t
+    sel = np.concatenate([np.arange(off[g], off[g + 1], dtype=np.int64) for g in kept] + [np.zeros(0, np.int64)])
+    return rows.index_select(0, t.from_numpy(sel).to(rows.device)), np.concatenate([[0], np.cumsum(np.diff(off)[kept])]).astype(np.int64)
+
+
+def best_candidates_local(x_unit, y_unit, x_off, y_off, k: int, margin: str):
+    """`best_candidates` inside every document pair: x_unit [n_x, d], y_unit [n_y, d] are contiguous fp16 / bf16 device
+    tensors of unit rows, pair g holds the source rows [x_off[g], x_off[g+1]) and the target rows [y_off[g], y_off[g+1]).
+    One grouped search per direction (FlatIndex.search_groups), then the list means and the candidate scoring once each
+    over all rows with global row ids -> (fwd_best int64 [n_x], fwd_score float32 [n_x], bwd_best int64 [n_y], bwd_score
+    float32 [n_y]) on the device; the best rows are global row numbers, always inside the row's own pair.  Every pair needs
+    k rows on both sides (as `best_candidates`); `mine_local` leaves the smaller ones out first."""
+    _margin_code(margin)
+    x_off, y_off = _group_offsets(x_off, y_off)
+    idx_x, idx_y = FlatIndex.over(x_unit), FlatIndex.over(y_unit)
+    if idx_x.d != idx_y.d or idx_x.storage != idx_y.storage:
+        raise ValueError("the two sides differ in dimension or storage type")
+    if int(x_off[-1]) != idx_x.ntotal or int(y_off[-1]) != idx_y.ntotal:
+        raise ValueError(f"the offsets end at {int(x_off[-1])} and {int(y_off[-1])} for {idx_x.ntotal} and {idx_y.ntotal} rows")
+    small = small_groups(x_off, y_off, k)
+    if small.any():
+        g = int(np.nonzero(small)[0][0])
+        raise ValueError(f"pair {g} holds {int(x_off[g + 1] - x_off[g])} and {int(y_off[g + 1] - y_off[g])} rows, fewer than k = {k}")
+    sims_xy, ids_xy = idx_y.search_groups(x_unit, k, x_off, y_off)   # x among the targets of its pair
+    sims_yx, ids_yx = idx_x.search_groups(y_unit, k, y_off, x_off)   # y among the sources of its pair
+    mean_x, mean_y = list_means(sims_xy), list_means(sims_yx)
+    fwd_best, fwd_score, _ = candidate_scores(sims_xy, ids_xy, mean_x, mean_y, margin)
+    bwd_best, bwd_score, _ = candidate_scores(sims_yx, ids_yx, mean_y, mean_x, margin)
+    return fwd_best, fwd_score, bwd_best, bwd_score
+
+
+def mine_local(x_unit, y_unit, x_off, y_off, k: int = 16, margin: str = "ratio", retrieval: str = "max", threshold=None,
+               stats: dict = None):
+    """Local mining: `mine_bitexts` inside every document pair, all pairs at once -> (scores float32 [p], src int64 [p],
+    tgt int64 [p], group int64 [p]) on the host, grouped by pair (ascending) and in `mine_bitexts`' output order inside a
+    pair; src and tgt are row numbers inside the pair's two documents.  A pair with fewer than k rows on either side is
+    left out before the search and yields nothing; stats["small_pairs"] (when a dict is given) counts them.
+    The retrieval step runs once over all pairs (`select_pairs` on global row numbers: one stable sort, for `max` one
+    greedy pass), then a stable partition by pair: pairs share no rows and a stable sort keeps each pair's internal order,
+    so this equals the per-pair passes."""
+    _margin_code(margin)
+    if retrieval not in RETRIEVALS:
+        raise ValueError(f"retrieval {retrieval!r}: one of {', '.join(RETRIEVALS)}")
+    x_off, y_off = _group_offsets(x_off, y_off)
+    small = small_groups(x_off, y_off, k)
+    if stats is not None:
+        stats["small_pairs"] = int(small.sum())
+    kept = np.nonzero(~small)[0]
+    if small.any():
+        x_unit, x_off = _pack_groups(x_unit, x_off, kept)
+        y_unit, y_off = _pack_groups(y_unit, y_off, kept)
+    if kept.size == 0:
+        return np.zeros(0, np.float32), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64)
+    score, src, tgt = select_pairs(*best_candidates_local(x_unit, y_unit, x_off, y_off, k, margin), retrieval=retrieval, threshold=threshold)
+    group = np.searchsorted(x_off, src, side="right") - 1
+    order = np.argsort(group, kind="stable")
+    score, src, tgt, group = score[order], src[order], tgt[order], group[order]
+    return score, src - x_off[group], tgt - y_off[group], kept[group]
 
 
 def xsim(x, y, k: int = 16, margin: str = "ratio", storage: str = "fp16") -> float:
