@@ -105,12 +105,21 @@ int svx_del_penalty(svx_ctx *ctx, const float *scores, int64_t n, double frac, d
 
 /* dense_traceback(bp) -> alignments                                            dp_utils.py:146-174
  * bp [s0+1][s1+1]; align [s0+s1][4] int32 rows (x_start, x_len, y_start, y_len) in document
- * order; *count = number of rows, or -SVX_ERR_* on failure. */
+ * order; *count = number of rows, or -SVX_ERR_* on failure.
+ * SVX_ERR_BP: a value other than 0 / 1 / 2 at a node of the walk, or a move that would leave the lattice (0 or 2 at
+ * x == 0, 0 or 1 at y == 0).  The reference wraps around through a negative numpy index on such a move; that is not
+ * mirrored.  No cell outside bp is ever addressed, whatever the table holds. */
 int svx_dense_traceback(svx_ctx *ctx, const int32_t *bp, int s0, int s1, int32_t *align, int32_t *count);
 
 /* sparse_traceback(csum, xp, yp, b_offset, xsize, ysize) -> (alignments, scores)  dp_utils.py:105-143
  * (+ process_scores :89-102).  align [xsize+ysize+2][4], scores [xsize+ysize+2] float64 (both are also
- * used as scratch by the walk), *count as above. */
+ * used as scratch by the walk: rows past *count are unspecified), *count as above.
+ * csum, xp, yp [a_out][B], b_offset_out [a_out]; the tables may hold anything.  Rule: no cell outside
+ * [0, a_out) x [0, B) is ever addressed.  A node (x, y) of the walk lives at [x + y][y - b_offset_out[x + y]]; the end
+ * node (xsize, ysize), every node the back-pointers lead to and the origin (0, 0) -- whose csum the first score is taken
+ * from -- must lie inside that rectangle, a back-pointer must be a step (px, py) >= 0, not (0, 0), with px <= x and
+ * py <= y, and a_out >= 1, B >= 1, xsize, ysize >= 0: anything else is SVX_ERR_TRACEBACK ('traceback bug') and no score
+ * is computed. */
 int svx_sparse_traceback(svx_ctx *ctx, const double *csum, const int32_t *xp, const int32_t *yp,
                          const int32_t *b_offset_out, int a_out, int B, int xsize, int ysize, int32_t *align,
                          double *scores, int32_t *count);

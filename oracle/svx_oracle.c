@@ -261,6 +261,9 @@ int orc_dense_traceback(const int32_t *bp, int s0, int s1, int32_t *out)
     int xx = s0, yy = s1, n = 0;
     while (!(xx == 0 && yy == 0)) {
         int b = bp[(long)xx * cmax + yy];
+        /* a move that would leave the lattice: the reference wraps around through a negative numpy
+         * index there, which is no behaviour to mirror; with this guard n never exceeds s0 + s1 */
+        if ((xx == 0 && (b == 0 || b == 2)) || (yy == 0 && (b == 0 || b == 1))) return -ORC_ERR_BP;
         int32_t *o = out + 4 * (long)n;
         if (b == 0)      { o[0] = xx - 1; o[1] = 1; o[2] = yy - 1; o[3] = 1; xx--; yy--; }
         else if (b == 1) { o[0] = xx;     o[1] = 0; o[2] = yy - 1; o[3] = 1; yy--; }

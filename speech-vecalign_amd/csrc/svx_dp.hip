@@ -94,6 +94,8 @@ __device__ int dense_traceback_thread(const int* bp, int s0, int s1, int* out, i
     while (!(xx == 0 && yy == 0)) {
         if (n >= cap) return -SVX_ERR_BP;
         const int b = bp[diag ? (size_t)(xx + yy) * rmax + xx : (size_t)xx * cmax + yy];
+        // a move that would leave the lattice (the reference wraps around through a negative numpy index there)
+        if ((xx == 0 && (b == 0 || b == 2)) || (yy == 0 && (b == 0 || b == 1))) return -SVX_ERR_BP;
         int* o = out + 4 * (size_t)(cap - 1 - n);  // fill from the back: document order at the end
         if (b == 0) { o[0] = xx - 1; o[1] = 1; o[2] = yy - 1; o[3] = 1; xx--; yy--; }
         else if (b == 1) { o[0] = xx; o[1] = 0; o[2] = yy - 1; o[3] = 1; yy--; }
@@ -811,6 +813,13 @@ __device__ void sparse_traceback_block(const TbArgs& g, char* smem) {
     const int Aout = g.Aout, B = g.B;
     const bool wide = g.bpk == nullptr;
     const bool cor = g.cw > 0;
+    if (Aout < 1 || B < 1 || g.xs < 0 || g.ys < 0) {  // no table to walk (uniform over the workgroup: nothing is loaded)
+        if (threadIdx.x == 0) {
+            *g.count = -SVX_ERR_TRACEBACK;
+            if (g.status) *g.status = SVX_ERR_TRACEBACK;
+        }
+        return;
+    }
     const size_t win_bytes = g.chunk > 0 ? (cor ? tb_win_bytes(g.chunk, g.cw, false) : tb_win_bytes(g.chunk, B, wide)) : 0;
     const int nwin = g.chunk > 0 ? (Aout + g.chunk - 1) / g.chunk : 1;
     int xx = __builtin_amdgcn_readfirstlane(g.xs), yy = __builtin_amdgcn_readfirstlane(g.ys), nw = 0, err = 0;  // walk state (wave-uniform: scalar registers)
@@ -872,6 +881,10 @@ __device__ void sparse_traceback_block(const TbArgs& g, char* smem) {
             const int aa = g.xs + g.ys;
             const int bb = (aa >= 0 && aa < Aout) ? g.ys - g.boff[aa] : -1;
             if (bb < 0 || bb >= B) err = SVX_ERR_TRACEBACK;
+        }
+        if (!err) {  // and so must the origin: the walk stops at (0,0) before it looks at the band, the score pass below reads
+            const int b0 = Aout >= 1 ? -g.boff[0] : -1;   // csum there (the reference indexes a_b_csum[0, bb] before its break)
+            if (b0 < 0 || b0 >= B) err = SVX_ERR_TRACEBACK;
         }
         sh_n = err ? -err : nw;
     }

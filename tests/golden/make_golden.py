@@ -299,8 +299,38 @@ def gen_records(ref):
     print("reference_records.json:", os.path.getsize(os.path.join(HERE, "reference_records.json")) // 1024, "KiB")
 
 
+def gen_tail(ref):
+    """tests/golden/tail_records.json: what the reference's own sparse_traceback, dense_traceback and upsample_alignment +
+    extend_alignments + alignment_to_search_path return on the success cases of tests/tail_ref.py (tables and alignments
+    that no DP produced), as sha256 digests (cases.digest()).  Failure cases are never run: with a (0,0) back-pointer the
+    reference does not terminate."""
+    import json
+    import tail_ref as T
+    R = ref.dp_utils
+    rec = {"sparse_traceback": {}, "dense_traceback": {}, "search_path": {}, "search_path_long": {}}
+    for name in T.TB_OK:
+        t = T.tb_ok_case(name)
+        with np.errstate(over="ignore"):
+            al, sc = R.sparse_traceback(t['csum'], t['xp'], t['yp'], t['boff'], t['N'], t['M'])
+        rec["sparse_traceback"][name] = {"alignments": digest(al, 'alignments'), "scores": digest(sc)}
+    for name in T.DENSE_OK:
+        rec["dense_traceback"][name] = digest(R.dense_traceback(T.dense_ok_case(name)), 'alignments')
+    for g in T.SP_GRID:
+        al = T.sp_alignment(g)
+        rec["search_path"][T.sp_id(g)] = {label: digest(T.ref_search_path(R, al, up, s0, s1), 'searchpath')
+                                          for label, up, s0, s1 in T.sp_calls(al)}
+    for rows in (T.SP_LDS_ROWS, T.SP_LDS_ROWS + 1):
+        al = T.sp_long(T.SP_LDS_ROWS + 1)[:rows]
+        rec["search_path_long"][str(rows)] = {label: digest(T.ref_search_path(R, al, up, s0, s1), 'searchpath')
+                                              for label, up, s0, s1 in T.sp_calls(al)[:3]}
+    with open(os.path.join(HERE, "tail_records.json"), "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("tail_records.json:", os.path.getsize(os.path.join(HERE, "tail_records.json")) // 1024, "KiB")
+
+
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["ops", "pipeline", "example", "example_full", "margin", "post", "example_files", "records"]
+    what = sys.argv[1:] or ["ops", "pipeline", "example", "example_full", "margin", "post", "example_files", "records", "tail"]
     if "post" in what:
         gen_post(ref_loader.REF_ROOT)
     if "example_files" in what:
@@ -319,3 +349,5 @@ if __name__ == "__main__":
             gen_example_full(ref)
     if "records" in what:
         gen_records(ref_loader.load())
+    if "tail" in what:
+        gen_tail(ref_loader.load())

@@ -564,9 +564,12 @@ def test_straight_narrow_band_vs_oracle(orc):
 
 @pytest.mark.parametrize("m2o", [None, 20])
 def test_band_too_wide_for_the_traceback_window_vs_oracle(orc, m2o):
-    """A band of 400 cells per diagonal leaves no room for a traceback window in LDS (tb_chunk() == 0): the walk then
-    reads band offsets and back-pointers from global memory -- packed bytes for the 10-type shape, int32 pairs when the
-    steps do not fit four bits (--many_to_one 20).  Same spans and scores as the oracle."""
+    """A band of 400 cells per diagonal leaves no room for a whole-diagonal traceback window in LDS (tb_chunk() == 0).
+    m2o = None (10 types, packed bytes): B > 320 and B % 16 == 0, so the walk runs tb_walk<3> on corridor windows of 64
+    diagonals x 320 columns; on this pair it stays within about 16 columns of the band centre, so the corridor never
+    moves (test_gpu_tail.py has pairs that make it move).  m2o = 20 (steps do not fit four bits, int32 pairs): B >= 159,
+    so the walk runs tb_walk<0> and reads band offsets and back-pointers from global memory.
+    Same spans and scores as the oracle."""
     from svx.vecalign import dp_utils
     from svx.vecalign.vecalign import resolve_search_params
     W = 200
