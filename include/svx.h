@@ -421,6 +421,57 @@ int svx_concat_rows(svx_ctx *ctx, int dtype, int d, const svx_pair *pairs, const
                     const svx_concat_params *params, int64_t cap, void *x_rows, void *y_rows, void *x_unit, void *y_unit,
                     int unit_dtype, int32_t *meta, int64_t *counts);
 
+/* ---- band search around a prior alignment (csrc/svx_prior.hip) ---------------------------------------------
+ * At max_depth == 0 dp_utils.vecalign() refines around the same-level alignment it has just made (dp_utils.py:485-489:
+ * alignment_to_search_path, make_sparse_costs, sparse_dp, sparse_traceback).  svx_align_around is that step started from
+ * an alignment the CALLER supplies: an earlier run, a cheap 1-1 pass, or the segments' timestamps (svx_time_prior).
+ *
+ * It is svx_align_batch in SVX_SEARCH_STRAIGHT -- the same random draws (depth 0 only, the index layout
+ * svx_norm_index_count / svx_knob_index_count give for max_size_full_dp = 1 << 30), normalisers, deletion penalty, final
+ * types, outputs, svx_debug_level view, stage timers and software pipeline -- except that the level-0 alignment the search
+ * path is made from is the prior instead of the one block covering both documents.  params->search_mode must be
+ * SVX_SEARCH_AROUND (svx_align_batch keeps rejecting that value).  priors: HOST array parallel to pairs; typically another
+ * call's svx_pair.align / .info with cap = n + m + 2, with no host round trip in between, or what svx_time_prior wrote.
+ * The call flushes the software pipeline first (svx_flush), so a prior that an earlier pipelined call on this context
+ * produces is complete when it is read; prior buffers must stay alive until svx_flush, like every input.
+ *
+ * The prior is taken in on the device, one workgroup per pair, with no host synchronisation, in this order:
+ *   info[1] != 0                                  the pair fails with that code;
+ *   count = info[0] outside [0, cap]              SVX_ERR_ARG;
+ *   a row with a negative length or both 0        SVX_ERR_PATH;
+ *   sum of x_len > n or sum of y_len > m          SVX_ERR_EXTEND;
+ *   sums smaller than n / m                       one final row (n - sum x_len, m - sum y_len) is appended, so count = 0 is
+ *                                                 exactly the straight search; a remainder with one side 0 is a deletion
+ *                                                 run, which alignment_to_search_path walks as a slant.
+ * Only the two lengths of a row are read.  A pair that fails gets the code in its info[1] (info[0] = 0) and the ingest
+ * writes nothing else for it; it never forms an address from its rows and does not disturb the other pairs of the batch.
+ * Returned at once with SVX_ERR_ARG and text, nothing queued: a null argument, cap < 0, a prior buffer that is the pair's
+ * own align / info output (in-place refinement is not supported), a band (2 * width_over2) above 64 cells -- the wide-band
+ * tile sweep stays straight-only: its ticket capacity is planned on the host from the straight geometry. */
+#define SVX_SEARCH_AROUND 2
+typedef struct svx_prior {
+    const int32_t *rows;   /* device [cap][4] rows (x_start, x_len, y_start, y_len); only the two lengths are read */
+    const int32_t *info;   /* device [2]: info[0] = number of rows, info[1] = 0 or SVX_ERR_* (layout of svx_pair.info) */
+    int32_t cap, pad;
+} svx_prior;
+int svx_align_around(svx_ctx *ctx, const svx_align_params *params, const svx_pair *pairs,
+                     const svx_prior *priors, int n_pairs);
+
+/* A prior from the segments' timestamps: parallel speech is time-synchronous up to a lag while segment indices drift apart
+ * wherever one side has a stretch the other lacks.  pairs: n and m are read; frames (HOST array of n_pairs) as
+ * svx_concat_rows reads it, F0 = frames[p].src [n][2], F1 = frames[p].tgt [m][2]; out (HOST array of n_pairs): rows / info
+ * are WRITTEN (device), cap >= n + m.
+ *   window of source segment i = floor(F0[i][0] / window), of target segment j = floor(max(F1[j][0] - lag, 0) / window),
+ *   in int64; window > 0, lag may be negative (|lag| < 2^62).
+ * One row per window value present on either side, windows ascending: x_start = source segments in earlier windows,
+ * x_len = source segments in this window, likewise y; info = (number of rows, 0).  The lengths always sum to n and m.
+ * Segment starts that decrease on a side give info = (0, SVX_ERR_PATH) and no rows.
+ * A null argument, window <= 0, negative sizes or cap < n + m return SVX_ERR_ARG with text and queue nothing.
+ * Asynchronous on the context's stream, no host synchronisation.  Scratch (the descriptors and 4 bytes per segment + 8 per
+ * pair) lives in the grow-only buffer of svx_alignment_rows, uploaded through the same pinned staging. */
+int svx_time_prior(svx_ctx *ctx, const svx_pair *pairs, const svx_frames *frames, int n_pairs,
+                   int64_t window, int64_t lag, const svx_prior *out);
+
 /* Per-level intermediates of the LAST svx_align_batch call on this context -- the entries of the `stack` the reference
  * returns (dp_utils.py:412-537) -- as device pointers into the context's scratch arena (valid until the next call;
  * the scalar fields are read back, which synchronises the stream).  Pointers are NULL for what a level does not have

@@ -46,6 +46,7 @@ struct BatchParams {
     int W, B, dtype, d, nsamp, n_types;
     double frac;
     bool straight, tiles, packable;
+    bool around;   // straight, with the level-0 alignment seeded from the caller's prior (svx_align_around)
 };
 
 // One half of a batch in flight (svx_align_batch, software pipeline): its own scratch arena, descriptors and launch
@@ -554,7 +555,8 @@ extern "C" int svx_debug_level(svx_ctx* ctx, int pair, int level, svx_level_view
 
 // ------------------------------------------------------------------------------ plan of one half
 // Level sizes, scratch layout (inside the half's own arena) and launch extents of pairs[0 .. n).
-static int plan_half(svx_ctx* ctx, HalfState& H, const BatchParams& bp, const svx_align_params* prm, const svx_pair* pairs, int n_pairs) {
+static int plan_half(svx_ctx* ctx, HalfState& H, const BatchParams& bp, const svx_align_params* prm, const svx_pair* pairs,
+                     const svx_prior* priors, int n_pairs) {
     const int d = bp.d;
     const size_t esz = bp.dtype == SVX_F32 ? 4 : 2;
     const SvxTypes& tfinal = bp.tfinal;
@@ -585,7 +587,12 @@ static int plan_half(svx_ctx* ctx, HalfState& H, const BatchParams& bp, const sv
         if (mx > in.k0) return svx_fail(ctx, SVX_ERR_OVERLAPS, "%d x overlaps requrested (via alignment_types), but vecs0 only has %d", mx, in.k0);
         if (my > in.k1) return svx_fail(ctx, SVX_ERR_OVERLAPS, "%d y overlaps requrested (via alignment_types), but vecs1 only has %d", my, in.k1);
         const int L = straight ? 0 : svx_num_levels(in.n, in.m, prm->max_size_full_dp);
-        P.straight = straight ? 1 : 0;
+        P.straight = (straight && !bp.around) ? 1 : 0;  // (k_init_batch seeds the covering block; around: k_prior_ingest seeds the prior)
+        if (bp.around) {
+            P.prior_rows = priors[p].rows;
+            P.prior_info = priors[p].info;
+            P.prior_cap = priors[p].cap;
+        }
         NEED(ctx, L < SVX_MAX_LEVELS, "pair %d: %d pyramid levels (max %d)", p, L + 1, SVX_MAX_LEVELS);
         P.v[0] = in.vecs0; P.v[1] = in.vecs1;
         P.K[0] = in.k0; P.K[1] = in.k1;
@@ -1010,6 +1017,10 @@ static int run_interleaved(svx_ctx* ctx, HalfState* front, HalfState* chain, boo
             front->upload_valid = true;
             hipLaunchKernelGGL(k_init_batch, dim3(front->n_pairs), dim3(64), 0, A, front->dpairs);
             SVX_LAUNCH_CHECK(ctx, "k_init_batch");
+            if (front->bp.around) {
+                int rc = svxl_prior_ingest_batch(ctx, front->dpairs, front->n_pairs);
+                if (rc) return rc;
+            }
             if (front->bp.nsamp == 0) {
                 // compute_norms returns ones without samples (dp_utils.py:356-357): rbar = 0 -> 1 - 0
                 for (int p = 0; p < front->n_pairs; p++)
@@ -1084,9 +1095,8 @@ extern "C" int svx_flush(svx_ctx* ctx) {
     return SVX_OK;
 }
 
-extern "C" int svx_align_batch(svx_ctx* ctx, const svx_align_params* prm, const svx_pair* pairs, int n_pairs) {
-    NEED(ctx, ctx && prm && (pairs || n_pairs == 0), "svx_align_batch: null argument");
-    if (n_pairs <= 0) return SVX_OK;
+// svx_align_batch (priors == nullptr) and svx_align_around
+static int align_impl(svx_ctx* ctx, const svx_align_params* prm, const svx_pair* pairs, const svx_prior* priors, int n_pairs) {
     const auto t_enter = std::chrono::steady_clock::now();
     svx_ctx_ext* cx = X(ctx);
     SVX_HIP(ctx, hipSetDevice(ctx->device));
@@ -1110,8 +1120,24 @@ extern "C" int svx_align_batch(svx_ctx* ctx, const svx_align_params* prm, const 
     int mx = 0, my = 0;
     for (int t = 0; t < bp.tfinal.n; t++) { if (bp.tfinal.x[t] > mx) mx = bp.tfinal.x[t]; if (bp.tfinal.y[t] > my) my = bp.tfinal.y[t]; }
     bp.packable = mx <= 15 && my <= 15;  // back-pointers fit 4 bits each
-    NEED(ctx, prm->search_mode == SVX_SEARCH_COARSE_TO_FINE || prm->search_mode == SVX_SEARCH_STRAIGHT, "svx_align_batch: unknown search_mode %d", prm->search_mode);
-    bp.straight = prm->search_mode == SVX_SEARCH_STRAIGHT;
+    bp.around = priors != nullptr;
+    if (bp.around) {
+        NEED(ctx, prm->search_mode == SVX_SEARCH_AROUND, "svx_align_around: search_mode must be SVX_SEARCH_AROUND (got %d)", prm->search_mode);
+        // the tile sweep plans its ticket capacity on the host from the straight geometry
+        NEED(ctx, bp.B <= 64, "svx_align_around: band of %d cells (2 * width_over2): at most 64 around a prior", bp.B);
+        for (int p = 0; p < n_pairs; p++) {
+            const svx_prior& q = priors[p];
+            NEED(ctx, q.cap >= 0, "svx_align_around: pair %d: prior cap %d", p, q.cap);
+            NEED(ctx, q.info && (q.rows || q.cap == 0), "svx_align_around: pair %d: null prior buffer", p);
+            NEED(ctx, (const void*)q.rows != (const void*)pairs[p].align && (const void*)q.info != (const void*)pairs[p].info,
+                 "svx_align_around: pair %d: the prior is the pair's own output buffer (in-place refinement is not supported)", p);
+        }
+        // a prior may be the output of an earlier pipelined call whose second half is still held back
+        if ((rc = svx_flush(ctx))) return rc;
+    } else {
+        NEED(ctx, prm->search_mode == SVX_SEARCH_COARSE_TO_FINE || prm->search_mode == SVX_SEARCH_STRAIGHT, "svx_align_batch: unknown search_mode %d", prm->search_mode);
+    }
+    bp.straight = bp.around || prm->search_mode == SVX_SEARCH_STRAIGHT;
     // straight search with a band wider than the one-workgroup DP kernel takes: wavefront of tiles (svx_tiles.hip)
     bp.tiles = bp.straight && bp.B > 64;
     // (shape: the two LDS-resident ones for the sets they take, else the general one; every set make_types accepts)
@@ -1128,7 +1154,7 @@ extern "C" int svx_align_batch(svx_ctx* ctx, const svx_align_params* prm, const 
         if (!piped) {
             if ((rc = svx_flush(ctx))) return rc;   // (what an earlier pipelined call left behind)
             HalfState& H = cx->half[0];
-            if ((rc = plan_half(ctx, H, bp, prm, pairs, n_pairs))) return rc;
+            if ((rc = plan_half(ctx, H, bp, prm, pairs, priors, n_pairs))) return rc;
             cx->last_split = 0;
             plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
             if ((rc = run_interleaved(ctx, &H, nullptr, false))) return rc;
@@ -1139,12 +1165,12 @@ extern "C" int svx_align_batch(svx_ctx* ctx, const svx_align_params* prm, const 
             HalfState &H0 = cx->half[0], &H1 = cx->half[1];
             if (H0.chain_pending && (rc = run_interleaved(ctx, nullptr, &H0, true))) return rc;  // (cannot happen; kept for safety)
             auto t0 = std::chrono::steady_clock::now();
-            if ((rc = plan_half(ctx, H0, bp, prm, pairs, n0))) return rc;
+            if ((rc = plan_half(ctx, H0, bp, prm, pairs, priors, n0))) return rc;
             plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             // first half's front beside the chain the previous call left behind
             if ((rc = run_interleaved(ctx, &H0, H1.chain_pending ? &H1 : nullptr, true))) return rc;
             t0 = std::chrono::steady_clock::now();
-            if ((rc = plan_half(ctx, H1, bp, prm, pairs + n0, n_pairs - n0))) return rc;
+            if ((rc = plan_half(ctx, H1, bp, prm, pairs + n0, priors ? priors + n0 : nullptr, n_pairs - n0))) return rc;
             plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             cx->last_split = n0;
             // second half's front beside the first half's chain; its own chain waits for the next call or svx_flush
@@ -1175,4 +1201,18 @@ extern "C" int svx_align_batch(svx_ctx* ctx, const svx_align_params* prm, const 
         cx->recs.clear();
     }
     return SVX_OK;
+}
+
+extern "C" int svx_align_batch(svx_ctx* ctx, const svx_align_params* prm, const svx_pair* pairs, int n_pairs) {
+    NEED(ctx, ctx && prm && (pairs || n_pairs == 0), "svx_align_batch: null argument");
+    if (n_pairs <= 0) return SVX_OK;
+    return align_impl(ctx, prm, pairs, nullptr, n_pairs);
+}
+
+extern "C" int svx_align_around(svx_ctx* ctx, const svx_align_params* prm, const svx_pair* pairs, const svx_prior* priors, int n_pairs) {
+    if (!ctx) return svx_fail(nullptr, SVX_ERR_ARG, "svx_align_around: ctx is NULL");
+    NEED(ctx, prm && ((pairs && priors) || n_pairs == 0), "svx_align_around: null argument");
+    if (n_pairs <= 0) return SVX_OK;
+    for (int p = 0; p < n_pairs; p++) NEED(ctx, pairs[p].align && pairs[p].info, "svx_align_around: pair %d: null pointer", p);
+    return align_impl(ctx, prm, pairs, priors, n_pairs);
 }

@@ -224,6 +224,11 @@ struct SvxPairDev {
     int* t_cnt;        // [t_nd]
     int* t_pref;       // [t_nd + 1] tiles before diagonal s
     int* t_flag;       // [t_cap] tile finished
+    // search around a prior alignment (svx_align_around, svx_prior.hip): the caller's rows, taken in where the straight
+    // search seeds its covering block; null in the other modes
+    const int* prior_rows;  // [prior_cap][4]
+    const int* prior_info;  // [2]
+    int prior_cap, prior_pad;
     SvxLevel lev[SVX_MAX_LEVELS];
 };
 
@@ -318,3 +323,5 @@ int svxl_search_path_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int d
                            int chunk_tamax);  // chunk_tamax <= 0: no band-cost chunks wanted
 int svxl_del_penalty(svx_ctx*, const float* scores, int64_t n, double frac, double* out);
 int svxl_del_penalty_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int max_levels, double frac);
+// prior alignments (svx_prior.hip)
+int svxl_prior_ingest_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs);

@@ -65,9 +65,18 @@ def parse_args(argv=None):
     p.add_argument("--ign_indices_dir", type=str, default=None,
                    help="if provided, then some segments will be ignored when loading embeddings.")
     # additive
-    p.add_argument("--mode", choices=["ref", "band", "dense"], default="ref",
+    p.add_argument("--mode", choices=["ref", "band", "dense", "around"], default="ref",
                    help="search region: ref = the reference's coarse-to-fine recursion (default); band = Sakoe-Chiba band of "
-                        "--band cells around the straight diagonal; dense = every cell of the lattice (include/svx.h: SVX_SEARCH_STRAIGHT)")
+                        "--band cells around the straight diagonal; dense = every cell of the lattice (include/svx.h: SVX_SEARCH_STRAIGHT); "
+                        "around = the reference-mode band around a prior alignment, without the pyramid (SVX_SEARCH_AROUND; "
+                        "needs --prior_dir or --prior time)")
+    p.add_argument("--prior_dir", type=str, default=None,
+                   help="--mode around: alignment files {prior_dir}/{src}-{tgt}/{s}-{t}.txt in this job's output format; a pair "
+                        "without one is dropped with a warning")
+    p.add_argument("--prior", choices=["time"], default=None,
+                   help="--mode around: time = blocks of --prior_window seconds from the segments' timestamps (svx_time_prior)")
+    p.add_argument("--prior_window", type=float, default=30.0, help="--prior time: window length, seconds")
+    p.add_argument("--prior_lag", type=float, default=0.0, help="--prior time: delay of the target side, seconds (may be negative)")
     p.add_argument("--band", type=int, default=2048, help="--mode band: cells per diagonal (2 * width_over2)")
     p.add_argument("--batch_size", type=int, default=32, help="document pairs per device pass")
     p.add_argument("--io_threads", type=int, default=None, help="host threads that parse / read ahead of the GPU (default: the CPU count, at most 32)")
@@ -97,6 +106,13 @@ def parse_args(argv=None):
                    help="also write {post_dir}/{src}-{tgt}/{s}-{t}.txt: the alignments after filter_by_cost --max_cost, concat_aligns and "
                         "filter_by_dur, one src_ids:tgt_ids per line (the audio filter filter_untrans_align is not part of this chain)")
     args = p.parse_args(argv)
+    if args.mode == "around":
+        if (args.prior_dir is None) == (args.prior is None):
+            p.error("--mode around takes exactly one of --prior_dir and --prior time")
+        if args.prior == "time" and not args.prior_window * PRIOR_SAMPLE_RATE >= 1:
+            p.error("--prior_window must be at least one sample")
+    elif args.prior_dir is not None or args.prior is not None:
+        p.error("--prior_dir / --prior need --mode around")
     if args.concat_max_num is not None and not 1 <= args.concat_max_num <= 8:
         p.error("--concat_max_num must be 1 .. 8")
     if args.min_dur is not None and args.min_dur < 0:
@@ -111,6 +127,19 @@ def parse_args(argv=None):
     if args.max_cost is not None and args.max_cost < 0:
         p.error("--max_cost must be >= 0")
     return args
+
+
+PRIOR_SAMPLE_RATE = 16000  # --prior time: seconds -> sample positions of the segment files
+
+
+def frames_wanted(args) -> bool:
+    """Whether the segment timestamps are read: for the post-filter chain or for a time prior."""
+    return post_chain_wanted(args) or getattr(args, "prior", None) == "time"
+
+
+def prior_path(args, p) -> Path:
+    """--prior_dir: the prior alignment file of a pair, named like its output file."""
+    return Path(args.prior_dir) / f"{args.src_lang}-{args.tgt_lang}" / os.path.basename(p.output_path)
 
 
 def post_chain_wanted(args) -> bool:
@@ -306,13 +335,17 @@ def _prepare_pair(p: VecalignData, args, src_k: int, tgt_k: int):
     se = read_embeddings_pinned(p.src_embed_path, args.is_stopes_embed, args.fp16_embed)
     te = read_embeddings_pinned(p.tgt_embed_path, args.is_stopes_embed, args.fp16_embed)
     fr = None
-    if post_chain_wanted(args):   # (start, end) sample positions per segment, for joining and the duration filter
+    if frames_wanted(args):   # (start, end) sample positions per segment, for joining, the duration filter and a time prior
         from ..utils.file_utils import read_segments
         fr = tuple(np.asarray(read_segments(path), dtype=np.int64).reshape(-1, 2) for path in (p.src_seg_path, p.tgt_seg_path))
         for f in fr:
             if len(f) and (f.min() < -2 ** 31 or f.max() >= 2 ** 31):
                 raise ValueError(f"{p.src_seg_path}: sample positions beyond int32")
-    return st, tt, se, te, fr
+    pr = None
+    if getattr(args, "prior_dir", None) is not None:
+        from ..utils.file_utils import read_alignments
+        pr = read_alignments(prior_path(args, p))
+    return st, tt, se, te, fr, pr
 
 
 def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Optional[int] = None, stats: Optional[dict] = None):
@@ -387,12 +420,12 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
             # ---- uploads on the copy stream (pinned -> device), then gather + align on the compute stream
             with torch.cuda.stream(copy_stream):
                 dev_in = [(torch.from_numpy(st).to(dev, non_blocking=True), torch.from_numpy(tt).to(dev, non_blocking=True),
-                           se.to(dev, non_blocking=True), te.to(dev, non_blocking=True)) for st, tt, se, te, _ in prepared]
+                           se.to(dev, non_blocking=True), te.to(dev, non_blocking=True)) for st, tt, se, te, _, _ in prepared]
                 up = torch.cuda.Event()
                 up.record(copy_stream)
             compute.wait_event(up)
             docs = []
-            for (st, tt, se, te, _), (dst, dtt, dse, dte) in zip(prepared, dev_in):
+            for (st, tt, se, te, _, _), (dst, dtt, dse, dte) in zip(prepared, dev_in):
                 for x in (dst, dtt, dse, dte):
                     x.record_stream(compute)
                 sv, tv = gather_candidates(dse, dst), gather_candidates(dte, dtt)
@@ -405,11 +438,18 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
                 w2, search = width_over2, "coarse_to_fine"
             elif mode == "band":
                 w2, search = max(3, (args.band + 1) // 2), "straight"
+            elif mode == "around":  # the reference-mode band around a prior, no pyramid
+                w2, search = width_over2, "around"
             else:  # dense: the band covers the lattice (width_over2 > max(N, M))
                 w2, search = max(max(int(sv.shape[1]), int(tv.shape[1])) for sv, tv in docs) + 1, "straight"
+            time_prior = mode == "around" and args.prior == "time"
+            priors = None if mode != "around" else [None if time_prior else q[5] for q in prepared]
             pb = PreparedBatch(docs, types, args.del_percentile_frac, w2, args.max_size_full_dp,
                                args.costs_sample_size, args.num_samps_for_norm, rngs=rngs, search=search,
-                               frames=[q[4] for q in prepared] if margin is not None and chain is not None else None)
+                               frames=[q[4] for q in prepared] if (margin is not None and chain is not None) or time_prior else None,
+                               priors=priors)
+            if time_prior:
+                pb.time_prior(int(round(args.prior_window * PRIOR_SAMPLE_RATE)), int(round(args.prior_lag * PRIOR_SAMPLE_RATE)))
             pb.run()
             if margin is not None:
                 margin.gather(pb)
@@ -468,6 +508,11 @@ def main(argv=None):
                             Path(args.seg_dir) / src_lang, Path(args.seg_dir) / tgt_lang,
                             Path(args.concat_dir) / src_lang, Path(args.concat_dir) / tgt_lang,
                             Path(args.embed_dir) / src_lang, Path(args.embed_dir) / tgt_lang, out_dir, ign)
+    if getattr(args, "prior_dir", None) is not None:
+        have = [p for p in valid if check_exist(prior_path(args, p))]
+        if len(have) < len(valid):
+            logger.warning(f"--prior_dir: {len(valid) - len(have)} of {len(valid)} pairs have no prior alignment and are dropped")
+        valid = have
     if args.n_shard > 1:
         # one process per GPU; document pairs are independent, so shards never communicate
         import torch

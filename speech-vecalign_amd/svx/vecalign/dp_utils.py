@@ -80,6 +80,20 @@ def alignments_to_rows(alignments):
     return rows
 
 
+def prior_rows_from_alignments(alignments):
+    """[([x ids], [y ids])] as read_alignments returns them -> int32 [r, 4] rows (x_start, x_len, y_start, y_len) of a
+    prior for search="around": the lengths are len() of the two lists, the starts the running sums of the lengths in
+    front (what the ids of a complete monotone alignment are; the ids themselves are not read, so a deletion's empty
+    list needs no start)."""
+    rows = np.zeros((len(alignments), 4), dtype=np.int32)
+    xs = ys = 0
+    for i, (x, y) in enumerate(alignments):
+        rows[i] = (xs, len(x), ys, len(y))
+        xs += len(x)
+        ys += len(y)
+    return rows
+
+
 def level_sizes(n, m, max_size_full_dp):
     """Sizes per depth, dp_utils.py:403-408."""
     L = _lib.load().svx_num_levels(int(n), int(m), int(max_size_full_dp))
@@ -159,15 +173,23 @@ class PreparedBatch:
     is built here once."""
 
     def __init__(self, pairs, final_alignment_types, del_percentile_frac, width_over2, max_size_full_dp,
-                 costs_sample_size, num_samps_for_norm, rngs=None, norms=None, device=None, search="coarse_to_fine", frames=None):
+                 costs_sample_size, num_samps_for_norm, rngs=None, norms=None, device=None, search="coarse_to_fine", frames=None,
+                 priors=None):
         """frames: per pair (src, tgt) segment timestamps, [n, 2] and [m, 2] (start, end) sample positions (read_segments);
         kept on the device as int32 for concat_rows().
         search: "coarse_to_fine" (the reference's recursion) or "straight" (band of half-width `width_over2`
         around the straight line from (0,0) to (N,M): Sakoe-Chiba / dense search, include/svx.h SVX_SEARCH_STRAIGHT;
-        no pyramid, so `max_size_full_dp` is ignored)."""
-        if search not in ("coarse_to_fine", "straight"):
-            raise ValueError("search must be 'coarse_to_fine' or 'straight'")
-        if search == "straight":
+        no pyramid, so `max_size_full_dp` is ignored), or "around": the straight search with the band laid around a prior
+        alignment instead of the straight line (svx_align_around; band of at most 64 cells).
+        priors (search="around" only): per pair one of (rows, info) device tensors (int32 [cap, 4] and [2]); another
+        PreparedBatch (its align / info slices: same pair order and sizes, read on the device when run() is called, with
+        no host round trip); a host list of alignments [(x_ids, y_ids), ...] as read_alignments returns
+        (prior_rows_from_alignments); or None, to be filled by time_prior() before run()."""
+        if search not in ("coarse_to_fine", "straight", "around"):
+            raise ValueError("search must be 'coarse_to_fine', 'straight' or 'around'")
+        if (priors is not None) != (search == "around"):
+            raise ValueError("priors go with search='around', and only with it")
+        if search != "coarse_to_fine":
             max_size_full_dp = 1 << 30  # depth 0 only: the random draws of a vecalign() call without pyramid levels
         ctx = _lib.context(device)
         self.ctx = ctx
@@ -217,7 +239,7 @@ class PreparedBatch:
         prm.costs_sample_size = int(costs_sample_size)
         prm.num_samps_for_norm = int(num_samps_for_norm)
         prm.del_percentile_frac = float(del_percentile_frac)
-        prm.search_mode = _lib.SVX_SEARCH_STRAIGHT if search == "straight" else _lib.SVX_SEARCH_COARSE_TO_FINE
+        prm.search_mode = {"straight": _lib.SVX_SEARCH_STRAIGHT, "around": _lib.SVX_SEARCH_AROUND}.get(search, _lib.SVX_SEARCH_COARSE_TO_FINE)
         self.prm = prm
         npairs = len(self.vecs)
         self.cpairs = (_lib.Pair * npairs)()
@@ -281,6 +303,58 @@ class PreparedBatch:
             c.scores = self.scores.data_ptr() + 8 * int(offs[i])
             c.info = self.info.data_ptr() + 8 * i
             c.del_pen = self.del_pen.data_ptr() + 8 * _lib.SVX_MAX_LEVELS * i
+        self.cpriors = None
+        if search == "around":
+            self._set_priors(priors)
+
+    def _set_priors(self, priors):
+        ctx, t = self.ctx, self.ctx.torch
+        npairs = len(self.vecs)
+        if isinstance(priors, PreparedBatch):
+            priors = [priors] * npairs
+        if len(priors) != npairs:
+            raise ValueError("priors: one per document pair")
+        self.cpriors = (_lib.Prior * npairs)()
+        self.prior_own = [None] * npairs   # (rows, info) tensors of this batch's own: what time_prior() fills
+        for i, pr in enumerate(priors):
+            c = self.cpriors[i]
+            if isinstance(pr, PreparedBatch):
+                if i >= len(pr.vecs) or int(pr.offs[i + 1] - pr.offs[i]) != int(self.offs[i + 1] - self.offs[i]):
+                    raise ValueError("prior batch: pair %d differs in size" % i)
+                c.rows = pr.align.data_ptr() + 16 * int(pr.offs[i])
+                c.info = pr.info.data_ptr() + 8 * i
+                c.cap = int(pr.offs[i + 1] - pr.offs[i])
+                self.keep.append(pr)
+                continue
+            if pr is None:
+                cap = int(self.offs[i + 1] - self.offs[i])
+                rows = t.zeros((cap, 4), dtype=t.int32, device=ctx.tdev)
+                info = t.zeros(2, dtype=t.int32, device=ctx.tdev)   # (no rows: the straight search, until time_prior())
+                self.prior_own[i] = (rows, info)
+            elif isinstance(pr, tuple) and len(pr) == 2 and t.is_tensor(pr[0]):
+                rows, info = pr
+                if rows.dtype != t.int32 or info.dtype != t.int32 or not rows.is_cuda or not info.is_cuda:
+                    raise ValueError("prior %d: (rows, info) must be int32 device tensors" % i)
+                if rows.dim() != 2 or rows.shape[1] != 4 or info.numel() < 2 or not rows.is_contiguous() or not info.is_contiguous():
+                    raise ValueError("prior %d: rows [cap, 4] and info [2], contiguous" % i)
+            else:
+                h = prior_rows_from_alignments(pr)
+                rows = t.from_numpy(h if len(h) else np.zeros((1, 4), np.int32)).to(ctx.tdev)
+                info = t.tensor([len(h), 0], dtype=t.int32).to(ctx.tdev)
+            c.rows, c.info, c.cap = rows.data_ptr(), info.data_ptr(), int(rows.shape[0])
+            self.keep.append((rows, info))
+
+    def time_prior(self, window, lag=0):
+        """Fill the priors of a search="around" batch from the segments' timestamps (svx_time_prior, include/svx.h): one
+        block per window of `window` samples, the target side shifted by `lag` samples.  Needs `frames` and priors given
+        as None.  Asynchronous on the current stream; run() then reads the rows on the device."""
+        if self.cpriors is None or any(o is None for o in self.prior_own):
+            raise ValueError("time_prior() needs search='around' with priors=[None, ...]")
+        if self.cframes is None:
+            raise ValueError("time_prior() needs the batch's frames")
+        ctx = self.ctx
+        ctx.use_current_stream()
+        ctx.check(ctx.lib.svx_time_prior(ctx.h, self.cpairs, self.cframes, len(self.vecs), int(window), int(lag), self.cpriors))
 
     def run(self):
         """Launch the whole pipeline for the batch (asynchronous on the current torch stream)."""
@@ -288,7 +362,11 @@ class PreparedBatch:
         ctx.use_current_stream()
         self.rows = self.h_rows = None   # (alignment_rows() of an earlier run)
         try:
-            ctx.check(ctx.lib.svx_align_batch(ctx.h, ctypes.byref(self.prm), self.cpairs, len(self.vecs)))
+            priors = getattr(self, "cpriors", None)
+            if priors is not None:
+                ctx.check(ctx.lib.svx_align_around(ctx.h, ctypes.byref(self.prm), self.cpairs, priors, len(self.vecs)))
+            else:
+                ctx.check(ctx.lib.svx_align_batch(ctx.h, ctypes.byref(self.prm), self.cpairs, len(self.vecs)))
         finally:   # a call that fails half way may already have queued work that reads this batch
             ctx.hold(self)
 
