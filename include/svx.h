@@ -52,7 +52,12 @@ int svx_synchronize(svx_ctx *ctx);
 /* Message of the last failure on this context (ctx may be NULL for svx_create failures). */
 const char *svx_last_error(const svx_ctx *ctx);
 const char *svx_version(void);
-/* Bytes of device scratch currently held by the context. */
+/* Bytes of device scratch currently held by the context: the arena and the post-processing scratch.
+ * The post-processing scratch is what svx_alignment_rows, svx_concat_rows, svx_knn_search_groups and svx_time_prior work
+ * in: one grow-only device buffer of the context's own, not in the arena -- the views of svx_debug_level stay valid --,
+ * shared by the four calls (they are ordered on the context's stream) and filled through two pinned staging buffers
+ * taken in turn, like svx_align_batch's descriptors.  It grows with 25 % slack behind one stream synchronisation and is
+ * released by svx_destroy. */
 int64_t svx_scratch_bytes(const svx_ctx *ctx);
 
 /* ---- the five native functions of dp_core.pyx (float32 buffers, like the reference) ----- */
@@ -227,8 +232,8 @@ int svx_knn_search(svx_ctx *ctx, const void *queries, int q_dtype, int64_t n, co
  * d, k, the dtypes and finite rows: the rules of svx_knn_search.  A violation, a null argument, an offset array that does not
  * start at 0 or decreases, a negative n_groups, or offsets that need 2^31 or more workgroups (a group of n_g queries takes
  * ceil(n_g / 64)) return SVX_ERR_ARG with text and queue nothing.  Asynchronous on the context's stream, no host
- * synchronisation.  Scratch (the two offset arrays and 8 bytes per workgroup) lives in the grow-only buffer of
- * svx_alignment_rows, counted in svx_scratch_bytes, and is uploaded through the same pinned staging. */
+ * synchronisation.  Scratch (the two offset arrays and 8 bytes per workgroup) is the context's post-processing scratch
+ * (svx_scratch_bytes). */
 int svx_knn_search_groups(svx_ctx *ctx, const void *queries, int q_dtype, const void *db, int db_dtype, int d, int k,
                           const int64_t *q_off, const int64_t *db_off, int n_groups, float *sims, int64_t *ids);
 
@@ -358,8 +363,7 @@ int svx_align_batch(svx_ctx *ctx, const svx_align_params *params, const svx_pair
  * SVX_MAX_DIM.  A violation, a null argument or an unknown dtype returns SVX_ERR_ARG with text and queues nothing.
  * Asynchronous on the context's stream, no host synchronisation; it calls svx_flush first, so with the software pipeline
  * on it still sees complete outputs.  Scratch (a copy of the descriptors, a chunk table, per-chunk counts and offsets)
- * lives in a grow-only buffer of the context's own, not in the arena -- the views of svx_debug_level stay valid --, is
- * counted in svx_scratch_bytes and is uploaded through pinned staging like svx_align_batch's descriptors. */
+ * is the context's post-processing scratch (svx_scratch_bytes). */
 int svx_alignment_rows(svx_ctx *ctx, int dtype, int d, const svx_pair *pairs, int n_pairs, double max_score, int64_t cap,
                        void *x_rows, void *y_rows, void *x_unit, void *y_unit, int unit_dtype, int32_t *src, int64_t *count);
 
@@ -369,7 +373,7 @@ int svx_alignment_rows(svx_ctx *ctx, int dtype, int d, const svx_pair *pairs, in
  * concat_aligns only joins alignments that are directly connected on both sides, so a joined alignment is a contiguous run
  * of segments on each side, and while that run is at most k0 x k1 segments its embedding is the candidate row
  * vecs0[x_len-1][x_start+x_len-1] as for svx_alignment_rows.  svx_concat_rows applies the chain to the alignment rows of a
- * batch and gathers the rows of every output that fits (csrc/svx_concatrows.hip).
+ * batch and gathers the rows of every output that fits (csrc/svx_alignrows.hip).
  *
  * pairs: as svx_alignment_rows reads them.  frames (HOST array of n_pairs): per pair the device arrays [n][2] and [m][2] of
  * (start, end) sample positions of the segments (svecalign/utils/file_utils.py read_segments); may be NULL only when
@@ -404,8 +408,8 @@ int svx_alignment_rows(svx_ctx *ctx, int dtype, int d, const svx_pair *pairs, in
  * non-positive sample_rate or NaN limits where frames are needed, and missing frames return SVX_ERR_ARG with text and queue
  * nothing.  Asynchronous on the context's stream, no host synchronisation, svx_flush first.  Seven launches (count, scan
  * and write of the base rows; count, scan and write of the outputs; gather) with no host round trip in between.  Scratch
- * is the grow-only buffer of svx_alignment_rows (here also the compacted base rows, 24 bytes per alignment row, and 16 bytes
- * per output up to cap), counted in svx_scratch_bytes, uploaded through the same pinned staging. */
+ * is the context's post-processing scratch (svx_scratch_bytes; here also the compacted base rows, 24 bytes per alignment
+ * row, and 16 bytes per output up to cap). */
 #define SVX_CONCAT_MAX 8
 typedef struct svx_frames { const int32_t *src, *tgt; } svx_frames;
 typedef struct svx_concat_params {
@@ -468,7 +472,7 @@ int svx_align_around(svx_ctx *ctx, const svx_align_params *params, const svx_pai
  * Segment starts that decrease on a side give info = (0, SVX_ERR_PATH) and no rows.
  * A null argument, window <= 0, negative sizes or cap < n + m return SVX_ERR_ARG with text and queue nothing.
  * Asynchronous on the context's stream, no host synchronisation.  Scratch (the descriptors and 4 bytes per segment + 8 per
- * pair) lives in the grow-only buffer of svx_alignment_rows, uploaded through the same pinned staging. */
+ * pair) is the context's post-processing scratch (svx_scratch_bytes). */
 int svx_time_prior(svx_ctx *ctx, const svx_pair *pairs, const svx_frames *frames, int n_pairs,
                    int64_t window, int64_t lag, const svx_prior *out);
 

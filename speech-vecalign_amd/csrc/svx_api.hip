@@ -149,10 +149,10 @@ int svx_create(int device_id, svx_ctx** out) {
     c->arena_used = 0;
     c->err[0] = 0;
     c->profiling = 0;
-    c->rows_buf = nullptr;
-    c->rows_bytes = 0;
-    c->rows_turn = 0;
-    for (int i = 0; i < 2; i++) { c->rows_pin[i] = nullptr; c->rows_pin_cap[i] = 0; c->rows_up[i] = nullptr; c->rows_up_valid[i] = 0; }
+    c->post_buf = nullptr;
+    c->post_bytes = 0;
+    c->post_turn = 0;
+    for (int i = 0; i < 2; i++) { c->post_pin[i] = nullptr; c->post_pin_cap[i] = 0; c->post_up[i] = nullptr; c->post_up_valid[i] = 0; }
     for (int i = 0; i < S_COUNT; i++) { c->ms[i] = -1.0; c->launches[i] = 0; }
     c->pipeline = 0;
     c->last_split = 0;
@@ -174,7 +174,7 @@ int svx_destroy(svx_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     if (c->chain_ready) (void)hipStreamSynchronize(c->chain);
     if (ctx->arena) (void)hipFree(ctx->arena);
-    svxl_alignrows_release(ctx);
+    svxl_scratch_release(ctx);
     drop_pending(c);
     for (auto& r : c->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     if (c->side_ready) {
@@ -218,7 +218,7 @@ const char* svx_last_error(const svx_ctx* ctx) { return ctx ? ctx->err : g_err; 
 int64_t svx_scratch_bytes(const svx_ctx* ctx) {
     if (!ctx) return 0;
     const svx_ctx_ext* c = static_cast<const svx_ctx_ext*>(ctx);
-    return (int64_t)(ctx->arena_bytes + c->half[0].arena_bytes + c->half[1].arena_bytes + ctx->rows_bytes);
+    return (int64_t)(ctx->arena_bytes + c->half[0].arena_bytes + c->half[1].arena_bytes + ctx->post_bytes);
 }
 
 int svx_set_pipeline(svx_ctx* ctx, int on) {
@@ -297,6 +297,58 @@ static int arena_reserve(svx_ctx* ctx, size_t bytes) {
     return SVX_OK;
 }
 
+// ------------------------------------------------------------------------------ post-processing scratch (svx_common.h)
+// The order of the steps is what keeps the host from writing into a pinned buffer an upload still reads: the turn's event
+// is waited for before that buffer is freed, regrown or handed out.
+int svxl_scratch_begin(svx_ctx* ctx, const char* who, size_t up_bytes, size_t dev_bytes, char** pin, char** dev) {
+    if (dev_bytes > ctx->post_bytes) {
+        SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier call may still read the old buffer)
+        if (ctx->post_buf) SVX_HIP(ctx, hipFree(ctx->post_buf));
+        ctx->post_buf = nullptr;
+        ctx->post_bytes = 0;
+        const size_t want = dev_bytes + dev_bytes / 4;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->post_buf), want);
+        if (e != hipSuccess) return svx_fail(ctx, SVX_ERR_NOMEM, "%s: hipMalloc(%zu) failed: %s", who, want, hipGetErrorString(e));
+        ctx->post_bytes = want;
+    }
+    const int turn = ctx->post_turn;
+    ctx->post_turn = 1 - turn;
+    if (!ctx->post_up[turn]) SVX_HIP(ctx, hipEventCreateWithFlags(&ctx->post_up[turn], hipEventDisableTiming));
+    if (ctx->post_up_valid[turn]) SVX_HIP(ctx, hipEventSynchronize(ctx->post_up[turn]));
+    if (up_bytes > ctx->post_pin_cap[turn]) {
+        if (ctx->post_pin[turn]) SVX_HIP(ctx, hipHostFree(ctx->post_pin[turn]));
+        ctx->post_pin[turn] = nullptr;
+        ctx->post_pin_cap[turn] = 0;
+        SVX_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->post_pin[turn]), up_bytes + up_bytes / 4, hipHostMallocDefault));
+        ctx->post_pin_cap[turn] = up_bytes + up_bytes / 4;
+    }
+    *pin = ctx->post_pin[turn];
+    *dev = ctx->post_buf;
+    return SVX_OK;
+}
+
+int svxl_scratch_upload(svx_ctx* ctx, size_t bytes) {
+    const int turn = 1 - ctx->post_turn;  // the buffer svxl_scratch_begin handed out
+    SVX_HIP(ctx, hipMemcpyAsync(ctx->post_buf, ctx->post_pin[turn], bytes, hipMemcpyHostToDevice, ctx->stream));
+    SVX_HIP(ctx, hipEventRecord(ctx->post_up[turn], ctx->stream));
+    ctx->post_up_valid[turn] = 1;
+    return SVX_OK;
+}
+
+void svxl_scratch_release(svx_ctx* ctx) {
+    if (ctx->post_buf) (void)hipFree(ctx->post_buf);
+    ctx->post_buf = nullptr;
+    ctx->post_bytes = 0;
+    for (int i = 0; i < 2; i++) {
+        if (ctx->post_pin[i]) (void)hipHostFree(ctx->post_pin[i]);
+        if (ctx->post_up[i]) (void)hipEventDestroy(ctx->post_up[i]);
+        ctx->post_pin[i] = nullptr;
+        ctx->post_pin_cap[i] = 0;
+        ctx->post_up[i] = nullptr;
+        ctx->post_up_valid[i] = 0;
+    }
+}
+
 struct Bump;
 template <class T>
 static inline void set_off(T*& p, Bump& b, size_t bytes);
@@ -336,9 +388,6 @@ static int check_dim(svx_ctx* ctx, int d) {
         return svx_fail(ctx, SVX_ERR_ARG, "embedding dimension %d: must be a positive multiple of 8, at most %d", d, SVX_MAX_DIM);
     return SVX_OK;
 }
-
-#define NEED(ctx, cond, ...) \
-    do { if (!(cond)) return svx_fail(ctx, SVX_ERR_ARG, __VA_ARGS__); } while (0)
 
 extern "C" {
 

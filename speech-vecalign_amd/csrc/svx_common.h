@@ -248,18 +248,25 @@ struct svx_ctx {
     size_t arena_used;
     char err[512];
     int profiling;
-    // svx_alignment_rows (svx_alignrows.hip): its descriptor copy, chunk table, counts and offsets live in a grow-only
-    // buffer of their own (the arena keeps the views of svx_debug_level), uploaded through two pinned buffers in turn
-    char* rows_buf;
-    size_t rows_bytes;
-    char* rows_pin[2];
-    size_t rows_pin_cap[2];
-    hipEvent_t rows_up[2];
-    int rows_up_valid[2];
-    int rows_turn;
+    // The post-processing scratch: one grow-only device buffer of the context's own (the arena keeps the views of
+    // svx_debug_level) and two pinned staging buffers taken in turn, so that the host may run a call ahead of the device
+    // without waiting for the upload of the call before.  Its users, ordered on the context's stream, each lay out the
+    // whole buffer anew: svx_alignment_rows and svx_concat_rows (svx_alignrows.hip: descriptors, chunk table, counts,
+    // offsets, compacted rows), svx_knn_search_groups (svx_groupsearch.hip: offsets, workgroup table) and svx_time_prior
+    // (svx_prior.hip: descriptors, prefix counts).  They go through svxl_scratch_begin / svxl_scratch_upload only.
+    char* post_buf;
+    size_t post_bytes;        // counted in svx_scratch_bytes
+    char* post_pin[2];
+    size_t post_pin_cap[2];
+    hipEvent_t post_up[2];    // the upload out of post_pin[i] is done
+    int post_up_valid[2];
+    int post_turn;            // the pinned buffer the next call takes
 };
 
 int svx_fail(svx_ctx* ctx, int code, const char* fmt, ...);
+#define NEED(ctx, cond, ...) \
+    do { if (!(cond)) return svx_fail(ctx, SVX_ERR_ARG, __VA_ARGS__); } while (0)
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 #define SVX_HIP(ctx, call)                                                                     \
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \
@@ -272,8 +279,12 @@ int svx_fail(svx_ctx* ctx, int code, const char* fmt, ...);
     } while (0)
 
 // ---- kernel launchers (defined in the .hip files) ---------------------------------------
-// alignment rows (svx_alignrows.hip)
-void svxl_alignrows_release(svx_ctx*);
+// post-processing scratch (svx_api.hip).  begin: the device buffer holds dev_bytes (grown behind a stream synchronise), the
+// turn's pinned buffer holds up_bytes and no upload reads it any more -> *pin to fill, *dev the device base; `who` names the
+// entry point in error texts.  upload: the first `bytes` of that pinned buffer go to the device base on the context's stream.
+int svxl_scratch_begin(svx_ctx*, const char* who, size_t up_bytes, size_t dev_bytes, char** pin, char** dev);
+int svxl_scratch_upload(svx_ctx*, size_t bytes);
+void svxl_scratch_release(svx_ctx*);
 // rows / pyramid (svx_rows.hip)
 int svxl_make_norm1(svx_ctx*, float* vecs, int64_t rows, int d);
 int svxl_pairsum(svx_ctx*, const float* vecs, int k, int n, int d, float* half, float* part, int nblk);

@@ -268,9 +268,6 @@ int launch_group_search(svx_ctx* ctx, const void* q, const void* db, int d, int 
 
 }  // namespace
 
-#define NEED(ctx, cond, ...) \
-    do { if (!(cond)) return svx_fail(ctx, SVX_ERR_ARG, __VA_ARGS__); } while (0)
-
 extern "C" int svx_knn_search_groups(svx_ctx* ctx, const void* queries, int q_dtype, const void* db, int db_dtype, int d, int k,
                                      const int64_t* q_off, const int64_t* db_off, int n_groups, float* sims, int64_t* ids) {
     if (!ctx) return svx_fail(nullptr, SVX_ERR_ARG, "svx_knn_search_groups: ctx is NULL");
@@ -293,33 +290,13 @@ extern "C" int svx_knn_search_groups(svx_ctx* ctx, const void* queries, int q_dt
     const long long n = q_off[n_groups], n_db = db_off[n_groups];
     NEED(ctx, (n == 0 || (queries && sims && ids)) && (n_db == 0 || db), "svx_knn_search_groups: null argument");
     if (n_blocks == 0) return SVX_OK;
-    hipStream_t st = ctx->stream;
-    // ---- scratch: [q_off][db_off][workgroup table], uploaded through the pinned staging of svx_alignment_rows
+    // ---- post-processing scratch: [q_off][db_off][workgroup table], all of it uploaded
     auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_off = up256((size_t)(n_groups + 1) * sizeof(long long)), b_tab = up256((size_t)n_blocks * sizeof(GroupBlock));
     const size_t b_up = 2 * b_off + b_tab;
-    if (b_up > ctx->rows_bytes) {
-        SVX_HIP(ctx, hipStreamSynchronize(st));  // (an earlier call may still read the old buffer)
-        if (ctx->rows_buf) SVX_HIP(ctx, hipFree(ctx->rows_buf));
-        ctx->rows_buf = nullptr;
-        ctx->rows_bytes = 0;
-        const size_t want = b_up + b_up / 4;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->rows_buf), want);
-        if (e != hipSuccess) return svx_fail(ctx, SVX_ERR_NOMEM, "svx_knn_search_groups: hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-        ctx->rows_bytes = want;
-    }
-    const int turn = ctx->rows_turn;
-    ctx->rows_turn = 1 - turn;
-    if (!ctx->rows_up[turn]) SVX_HIP(ctx, hipEventCreateWithFlags(&ctx->rows_up[turn], hipEventDisableTiming));
-    if (ctx->rows_up_valid[turn]) SVX_HIP(ctx, hipEventSynchronize(ctx->rows_up[turn]));
-    if (b_up > ctx->rows_pin_cap[turn]) {
-        if (ctx->rows_pin[turn]) SVX_HIP(ctx, hipHostFree(ctx->rows_pin[turn]));
-        ctx->rows_pin[turn] = nullptr;
-        ctx->rows_pin_cap[turn] = 0;
-        SVX_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->rows_pin[turn]), b_up + b_up / 4, hipHostMallocDefault));
-        ctx->rows_pin_cap[turn] = b_up + b_up / 4;
-    }
-    char* pin = ctx->rows_pin[turn];
+    char *pin, *dev;
+    int rc = svxl_scratch_begin(ctx, "svx_knn_search_groups", b_up, b_up, &pin, &dev);
+    if (rc) return rc;
     memcpy(pin, q_off, (size_t)(n_groups + 1) * sizeof(long long));
     memcpy(pin + b_off, db_off, (size_t)(n_groups + 1) * sizeof(long long));
     GroupBlock* ht = reinterpret_cast<GroupBlock*>(pin + 2 * b_off);
@@ -332,12 +309,11 @@ extern "C" int svx_knn_search_groups(svx_ctx* ctx, const void* queries, int q_dt
             at++;
         }
     }
-    SVX_HIP(ctx, hipMemcpyAsync(ctx->rows_buf, pin, b_up, hipMemcpyHostToDevice, st));
-    SVX_HIP(ctx, hipEventRecord(ctx->rows_up[turn], st));
-    ctx->rows_up_valid[turn] = 1;
-    const long long* dq = reinterpret_cast<const long long*>(ctx->rows_buf);
-    const long long* dd = reinterpret_cast<const long long*>(ctx->rows_buf + b_off);
-    const GroupBlock* dt = reinterpret_cast<const GroupBlock*>(ctx->rows_buf + 2 * b_off);
+    rc = svxl_scratch_upload(ctx, b_up);
+    if (rc) return rc;
+    const long long* dq = reinterpret_cast<const long long*>(dev);
+    const long long* dd = reinterpret_cast<const long long*>(dev + b_off);
+    const GroupBlock* dt = reinterpret_cast<const GroupBlock*>(dev + 2 * b_off);
     const bool bf = db_dtype == SVX_BF16;
     long long* gi = reinterpret_cast<long long*>(ids);
     switch (q_dtype) {

@@ -393,9 +393,6 @@ static int launch_knn_rpw(svx_ctx* ctx, const void* q, long n, const void* db, l
     return launch_knn<BF, QE, 1, 4>(ctx, q, n, db, N, d, k, out, st_in, st_out);
 }
 
-#define NEED(ctx, cond, ...) \
-    do { if (!(cond)) return svx_fail(ctx, SVX_ERR_ARG, __VA_ARGS__); } while (0)
-
 static int check_margin_dim(svx_ctx* ctx, int d) {
     if (d <= 0 || d % 32 != 0 || d > 32 * KNN_KSTEPS)
         return svx_fail(ctx, SVX_ERR_ARG, "embedding dimension %d: must be a positive multiple of 32, at most %d", d, 32 * KNN_KSTEPS);

@@ -110,8 +110,6 @@ static unsigned mine_grid(int64_t n) {
     return (unsigned)(g < MINE_MAXGRID ? g : MINE_MAXGRID);
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 template <int MARGIN>
 static void launch_candidates(svx_ctx* ctx, const float* sims, const long long* ids, long n, int k, const float* mean_q,
                               const float* mean_db, long n_db, long long id_base, float* scores, long long* best_id, float* best_score) {
@@ -121,9 +119,6 @@ static void launch_candidates(svx_ctx* ctx, const float* sims, const long long* 
     else
         k_margin_candidates<MARGIN, false><<<grid, block, 0, ctx->stream>>>(sims, ids, n, k, mean_q, mean_db, n_db, id_base, scores, best_id, best_score);
 }
-
-#define NEED(ctx, cond, ...) \
-    do { if (!(cond)) return svx_fail(ctx, SVX_ERR_ARG, __VA_ARGS__); } while (0)
 
 extern "C" {
 

@@ -188,12 +188,7 @@ __global__ __launch_bounds__(256) void k_time_prior(const TimePair* __restrict__
     if (tid == 0) { gst(P.info, total[0] + total[1]); gst(P.info + 1, 0); }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
-
-#define NEED(ctx, cond, ...) \
-    do { if (!(cond)) return svx_fail(ctx, SVX_ERR_ARG, __VA_ARGS__); } while (0)
 
 int svxl_prior_ingest_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs) {
     if (n_pairs <= 0) return SVX_OK;
@@ -226,29 +221,11 @@ extern "C" int svx_time_prior(svx_ctx* ctx, const svx_pair* pairs, const svx_fra
     hipStream_t st = ctx->stream;
     // ---- scratch: [descriptors][prefix counts]; the descriptors are uploaded
     const size_t b_up = up256((size_t)n_pairs * sizeof(TimePair)), b_all = b_up + up256(ints * sizeof(int));
-    if (b_all > ctx->rows_bytes) {
-        SVX_HIP(ctx, hipStreamSynchronize(st));  // (an earlier call may still read the old buffer)
-        if (ctx->rows_buf) SVX_HIP(ctx, hipFree(ctx->rows_buf));
-        ctx->rows_buf = nullptr;
-        ctx->rows_bytes = 0;
-        const size_t want = b_all + b_all / 4;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->rows_buf), want);
-        if (e != hipSuccess) return svx_fail(ctx, SVX_ERR_NOMEM, "svx_time_prior: hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-        ctx->rows_bytes = want;
-    }
-    const int turn = ctx->rows_turn;
-    ctx->rows_turn = 1 - turn;
-    if (!ctx->rows_up[turn]) SVX_HIP(ctx, hipEventCreateWithFlags(&ctx->rows_up[turn], hipEventDisableTiming));
-    if (ctx->rows_up_valid[turn]) SVX_HIP(ctx, hipEventSynchronize(ctx->rows_up[turn]));
-    if (b_up > ctx->rows_pin_cap[turn]) {
-        if (ctx->rows_pin[turn]) SVX_HIP(ctx, hipHostFree(ctx->rows_pin[turn]));
-        ctx->rows_pin[turn] = nullptr;
-        ctx->rows_pin_cap[turn] = 0;
-        SVX_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->rows_pin[turn]), b_up + b_up / 4, hipHostMallocDefault));
-        ctx->rows_pin_cap[turn] = b_up + b_up / 4;
-    }
-    TimePair* hp = reinterpret_cast<TimePair*>(ctx->rows_pin[turn]);
-    int* pre = reinterpret_cast<int*>(ctx->rows_buf + b_up);
+    char *pin, *dev;
+    int rc = svxl_scratch_begin(ctx, "svx_time_prior", b_up, b_all, &pin, &dev);
+    if (rc) return rc;
+    TimePair* hp = reinterpret_cast<TimePair*>(pin);
+    int* pre = reinterpret_cast<int*>(dev + b_up);
     for (int p = 0; p < n_pairs; p++) {
         const svx_pair& q = pairs[p];
         TimePair& r = hp[p];
@@ -260,10 +237,9 @@ extern "C" int svx_time_prior(svx_ctx* ctx, const svx_pair* pairs, const svx_fra
         r.pre[1] = pre + q.n + 1;
         pre += (size_t)q.n + q.m + 2;
     }
-    SVX_HIP(ctx, hipMemcpyAsync(ctx->rows_buf, ctx->rows_pin[turn], (size_t)n_pairs * sizeof(TimePair), hipMemcpyHostToDevice, st));
-    SVX_HIP(ctx, hipEventRecord(ctx->rows_up[turn], st));
-    ctx->rows_up_valid[turn] = 1;
-    hipLaunchKernelGGL(k_time_prior, dim3(n_pairs), dim3(256), 0, st, reinterpret_cast<const TimePair*>(ctx->rows_buf),
+    rc = svxl_scratch_upload(ctx, (size_t)n_pairs * sizeof(TimePair));  // (behind them the upload area is padding)
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_time_prior, dim3(n_pairs), dim3(256), 0, st, reinterpret_cast<const TimePair*>(dev),
                        (long long)window, (long long)lag);
     SVX_LAUNCH_CHECK(ctx, "k_time_prior");
     return SVX_OK;

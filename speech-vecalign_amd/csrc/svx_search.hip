@@ -271,9 +271,6 @@ static int launch_search(svx_ctx* ctx, const void* q, long n, const void* db, lo
     return SVX_OK;
 }
 
-#define NEED(ctx, cond, ...) \
-    do { if (!(cond)) return svx_fail(ctx, SVX_ERR_ARG, __VA_ARGS__); } while (0)
-
 extern "C" int svx_knn_search(svx_ctx* ctx, const void* queries, int q_dtype, int64_t n, const void* db, int db_dtype, int64_t n_db,
                               int d, int k, int64_t id_base, float* sims, int64_t* ids, int first) {
     NEED(ctx, ctx && (n == 0 || (queries && sims && ids)) && (n_db == 0 || db), "svx_knn_search: null argument");
