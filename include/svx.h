@@ -53,9 +53,9 @@ int svx_synchronize(svx_ctx *ctx);
 const char *svx_last_error(const svx_ctx *ctx);
 const char *svx_version(void);
 /* Bytes of device scratch currently held by the context: the arena and the post-processing scratch.
- * The post-processing scratch is what svx_alignment_rows, svx_concat_rows, svx_knn_search_groups and svx_time_prior work
- * in: one grow-only device buffer of the context's own, not in the arena -- the views of svx_debug_level stay valid --,
- * shared by the four calls (they are ordered on the context's stream) and filled through two pinned staging buffers
+ * The post-processing scratch is what svx_alignment_rows, svx_concat_rows, svx_knn_search_groups, svx_time_prior and
+ * svx_prior_width work in: one grow-only device buffer of the context's own, not in the arena -- the views of svx_debug_level stay valid --,
+ * shared by these calls (they are ordered on the context's stream) and filled through two pinned staging buffers
  * taken in turn, like svx_align_batch's descriptors.  It grows with 25 % slack behind one stream synchronisation and is
  * released by svx_destroy. */
 int64_t svx_scratch_bytes(const svx_ctx *ctx);
@@ -450,9 +450,18 @@ int svx_concat_rows(svx_ctx *ctx, int dtype, int d, const svx_pair *pairs, const
  * Only the two lengths of a row are read.  A pair that fails gets the code in its info[1] (info[0] = 0) and the ingest
  * writes nothing else for it; it never forms an address from its rows and does not disturb the other pairs of the batch.
  * Returned at once with SVX_ERR_ARG and text, nothing queued: a null argument, cap < 0, a prior buffer that is the pair's
- * own align / info output (in-place refinement is not supported), a band (2 * width_over2) above 64 cells -- the wide-band
- * tile sweep stays straight-only: its ticket capacity is planned on the host from the straight geometry. */
+ * own align / info output (in-place refinement is not supported), a band (2 * width_over2) above 64 cells under
+ * SVX_SEARCH_AROUND (wider bands are SVX_SEARCH_AROUND_WIDE's).
+ *
+ * SVX_SEARCH_AROUND_WIDE is SVX_SEARCH_AROUND without the limit on the band: the same prior, ingest rules, draws,
+ * normalisers, penalty, outputs and flush-first behaviour (svx_align_batch rejects this value too).  A band of at most 64
+ * cells runs the very kernels of SVX_SEARCH_AROUND: outputs and svx_debug_level views are equal bit for bit.  A wider band
+ * runs the tile sweep of SVX_SEARCH_STRAIGHT around the prior's search path: every type set the wide straight sweep takes
+ * (SVX_ERR_ARG with the same text for a set no tile shape takes), never pipelined, and a svx_level_view like the wide
+ * straight sweep's (no a_b_costs; csum and back-pointers on lattice nodes only).  Time and scratch of the sweep grow with
+ * the band, not with n x m: a prior that follows the drift needs a band as wide as its blocks (svx_prior_width). */
 #define SVX_SEARCH_AROUND 2
+#define SVX_SEARCH_AROUND_WIDE 3
 typedef struct svx_prior {
     const int32_t *rows;   /* device [cap][4] rows (x_start, x_len, y_start, y_len); only the two lengths are read */
     const int32_t *info;   /* device [2]: info[0] = number of rows, info[1] = 0 or SVX_ERR_* (layout of svx_pair.info) */
@@ -475,6 +484,21 @@ int svx_align_around(svx_ctx *ctx, const svx_align_params *params, const svx_pai
  * pair) is the context's post-processing scratch (svx_scratch_bytes). */
 int svx_time_prior(svx_ctx *ctx, const svx_pair *pairs, const svx_frames *frames, int n_pairs,
                    int64_t window, int64_t lag, const svx_prior *out);
+
+/* The width_over2 from which the band around a prior holds every node of every block of that prior.  pairs (n and m are
+ * read) and priors: HOST arrays as svx_align_around takes them; width: DEVICE int32 [n_pairs], written.  One workgroup per
+ * pair applies the ingest rules of svx_align_around in their order and writes
+ *   1 + max over the ingested rows, the appended remainder row included, of min(x_len, y_len), and never less than 3
+ *   (the width svx_align_around raises smaller ones to);   0 for a prior the ingest would fail.
+ * Covering property: with that width_over2 every lattice node (x, y) of every ingested block -- x and y inside the
+ * block's two spans, ends included -- satisfies 0 <= y - new_b_offset[x + y] < 2 * width_over2, so the search can reach
+ * every alignment that stays inside the prior's blocks.  This rests on a check on the CPU oracle (tests/
+ * test_around_wide_cpu.py: block priors of 1 .. 15 blocks, deletion rows, a remainder), not on a proof; a deletion row
+ * counts with min = 0 because alignment_to_search_path merges deletion runs into the slant that follows.
+ * A null argument, negative sizes or cap, or a null prior buffer return SVX_ERR_ARG with text and queue nothing.
+ * Asynchronous on the context's stream, no host synchronisation.  Scratch: the descriptors only, in the context's
+ * post-processing scratch (svx_scratch_bytes). */
+int svx_prior_width(svx_ctx *ctx, const svx_pair *pairs, const svx_prior *priors, int n_pairs, int32_t *width);
 
 /* Per-level intermediates of the LAST svx_align_batch call on this context -- the entries of the `stack` the reference
  * returns (dp_utils.py:412-537) -- as device pointers into the context's scratch arena (valid until the next call;

@@ -758,6 +758,12 @@ static int plan_half(svx_ctx* ctx, HalfState& H, const BatchParams& bp, const sv
         if (tiles) {
             const long long TI = in.n / 32 + 1, TJ = in.m / 32 + 1;  // tiles of 32 x 32 nodes over (n + 1) x (m + 1)
             P.t_nd = (int)(TI + TJ - 1);
+            // Flags per tile anti-diagonal s, for ANY search path (straight line or prior).  The tiles of s hold the nodes
+            // of the node diagonals a = 32 s .. 32 s + 62.  A path point per diagonal with unit steps makes b_offset_out
+            // non-decreasing and growing by at most 1 per diagonal, so over these 63 diagonals the band rows
+            // [bo[a], bo[a] + B) form ONE interval of at most B + 62 values of y (consecutive intervals overlap: the run
+            // of band tiles of a diagonal is contiguous).  An interval of L values meets at most floor((L - 1) / 32) + 2
+            // tile columns: floor((B + 61) / 32) + 2 <= (B + 64) / 32 + 2.  k_tile_ranges checks the sum on the device.
             long long tcap = (long long)P.t_nd * ((B + 64) / 32 + 2);
             if (tcap > TI * TJ) tcap = TI * TJ;
             NEED(ctx, tcap < (1ll << 30), "pair %d: too many tiles", p);
@@ -1171,9 +1177,11 @@ static int align_impl(svx_ctx* ctx, const svx_align_params* prm, const svx_pair*
     bp.packable = mx <= 15 && my <= 15;  // back-pointers fit 4 bits each
     bp.around = priors != nullptr;
     if (bp.around) {
-        NEED(ctx, prm->search_mode == SVX_SEARCH_AROUND, "svx_align_around: search_mode must be SVX_SEARCH_AROUND (got %d)", prm->search_mode);
-        // the tile sweep plans its ticket capacity on the host from the straight geometry
-        NEED(ctx, bp.B <= 64, "svx_align_around: band of %d cells (2 * width_over2): at most 64 around a prior", bp.B);
+        NEED(ctx, prm->search_mode == SVX_SEARCH_AROUND || prm->search_mode == SVX_SEARCH_AROUND_WIDE,
+             "svx_align_around: search_mode must be SVX_SEARCH_AROUND or SVX_SEARCH_AROUND_WIDE (got %d)", prm->search_mode);
+        // SVX_SEARCH_AROUND keeps its limit; SVX_SEARCH_AROUND_WIDE hands wider bands to the tile sweep (below)
+        NEED(ctx, bp.B <= 64 || prm->search_mode == SVX_SEARCH_AROUND_WIDE,
+             "svx_align_around: band of %d cells (2 * width_over2): at most 64 around a prior", bp.B);
         for (int p = 0; p < n_pairs; p++) {
             const svx_prior& q = priors[p];
             NEED(ctx, q.cap >= 0, "svx_align_around: pair %d: prior cap %d", p, q.cap);
@@ -1187,7 +1195,8 @@ static int align_impl(svx_ctx* ctx, const svx_align_params* prm, const svx_pair*
         NEED(ctx, prm->search_mode == SVX_SEARCH_COARSE_TO_FINE || prm->search_mode == SVX_SEARCH_STRAIGHT, "svx_align_batch: unknown search_mode %d", prm->search_mode);
     }
     bp.straight = bp.around || prm->search_mode == SVX_SEARCH_STRAIGHT;
-    // straight search with a band wider than the one-workgroup DP kernel takes: wavefront of tiles (svx_tiles.hip)
+    // straight search, or search around a prior, with a band wider than the one-workgroup DP kernel takes: wavefront of
+    // tiles (svx_tiles.hip).  The sweep takes its geometry from the level's search path, whatever made that path.
     bp.tiles = bp.straight && bp.B > 64;
     // (shape: the two LDS-resident ones for the sets they take, else the general one; every set make_types accepts)
     if (bp.tiles) NEED(ctx, bp.tfinal.n >= 1 && svxl_band_tiles_shape(bp.tfinal) >= 0, "wide straight band: no tile shape takes these %d alignment types", bp.tfinal.n);

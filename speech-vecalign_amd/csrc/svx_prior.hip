@@ -4,6 +4,8 @@
 //                   the two length sums and of the "bad row" flag), appends the remainder row and copies the lengths into
 //                   lev[0].align / n_align -- where k_init_batch seeds the covering block of the straight search, so the
 //                   search-path, band-cost, DP and traceback kernels run unchanged.
+//   k_prior_width   one workgroup per pair: the same validation, then the width_over2 at which the band around the
+//                   prior's search path covers every block of the prior (svx_prior_width).
 //   k_time_prior    one workgroup per pair: a prior from the segments' timestamps.  A segment is the HEAD of a run when its
 //                   window differs from its predecessor's.  A window present on the source side gives the row of its
 //                   source head; a window present on the target side only gives the row of its target head.  The rank of a
@@ -26,6 +28,41 @@ __device__ __forceinline__ long long block_sum_ll(long long v, long long* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// Maximum of v (>= 0) over the workgroup, every thread gets it.
+__device__ __forceinline__ int block_max_int(int v, long long* red) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const long long a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
+    return (int)(a > b ? a : b);
+}
+
+// The ingest rules of svx_align_around in their order (include/svx.h) -> 0 with the two length sums, or the pair's
+// failure code.  count, code and the result are uniform over the workgroup: every caller's branch on them is taken by
+// all threads or by none.
+__device__ __forceinline__ int prior_check(const int* rows, int count, int code, int cap, int n, int m, long long* red,
+                                           long long* sx_out, long long* sy_out) {
+    if (code != 0) return code;
+    if (count < 0 || count > cap) return (int)SVX_ERR_ARG;
+    long long sx = 0, sy = 0, bad = 0;
+    for (int i = threadIdx.x; i < count; i += 256) {
+        const int xl = gld(rows + 4 * (size_t)i + 1), yl = gld(rows + 4 * (size_t)i + 3);
+        bad |= (xl < 0 || yl < 0 || (xl == 0 && yl == 0)) ? 1 : 0;
+        sx += xl;
+        sy += yl;
+    }
+    bad = block_sum_ll(bad, red);
+    if (bad != 0) return (int)SVX_ERR_PATH;  // (the sums mean nothing then)
+    sx = block_sum_ll(sx, red);
+    sy = block_sum_ll(sy, red);
+    if (sx > n || sy > m) return (int)SVX_ERR_EXTEND;
+    *sx_out = sx;
+    *sy_out = sy;
+    return 0;
+}
+
 __global__ __launch_bounds__(256) void k_prior_ingest(const SvxPairDev* __restrict__ pairs) {
     __shared__ long long red[4];
     const SvxPairDev& P = pairs[blockIdx.x];
@@ -33,31 +70,10 @@ __global__ __launch_bounds__(256) void k_prior_ingest(const SvxPairDev* __restri
     const int tid = threadIdx.x;
     const int count = gld(P.prior_info), code = gld(P.prior_info + 1);
     const int n = P.lev[0].n[0], m = P.lev[0].n[1];
-    // (count and code are uniform over the workgroup: every branch below is taken by all threads or by none)
-    if (code != 0) {
-        if (tid == 0) gst(P.status, code);
-        return;
-    }
-    if (count < 0 || count > P.prior_cap) {
-        if (tid == 0) gst(P.status, (int)SVX_ERR_ARG);
-        return;
-    }
-    long long sx = 0, sy = 0, bad = 0;
-    for (int i = tid; i < count; i += 256) {
-        const int xl = gld(rows + 4 * (size_t)i + 1), yl = gld(rows + 4 * (size_t)i + 3);
-        bad |= (xl < 0 || yl < 0 || (xl == 0 && yl == 0)) ? 1 : 0;
-        sx += xl;
-        sy += yl;
-    }
-    bad = block_sum_ll(bad, red);
-    if (bad != 0) {  // (the sums mean nothing then)
-        if (tid == 0) gst(P.status, (int)SVX_ERR_PATH);
-        return;
-    }
-    sx = block_sum_ll(sx, red);
-    sy = block_sum_ll(sy, red);
-    if (sx > n || sy > m) {
-        if (tid == 0) gst(P.status, (int)SVX_ERR_EXTEND);
+    long long sx = 0, sy = 0;
+    const int fail = prior_check(rows, count, code, P.prior_cap, n, m, red, &sx, &sy);
+    if (fail != 0) {
+        if (tid == 0) gst(P.status, fail);
         return;
     }
     // every row takes at least one segment of a side, so count <= sx + sy <= n + m: the rows and the remainder fit the
@@ -75,6 +91,41 @@ __global__ __launch_bounds__(256) void k_prior_ingest(const SvxPairDev* __restri
             total++;
         }
         gst(P.lev[0].n_align, total);
+    }
+}
+
+// ------------------------------------------------------------------------------ covering width
+struct WidthPair {
+    const int* rows;   // [cap][4]
+    const int* info;   // [2]
+    int* out;          // the pair's slot of width[]
+    int cap, n, m, pad;
+};
+
+// width_over2 from which the band around the prior's search path holds every node of every ingested block:
+// 1 + max over the rows the ingest would hand to the path kernel (remainder row included) of min(x_len, y_len), at
+// least 3 (what svx_align_around raises smaller widths to); 0 for a prior the ingest would fail.
+__global__ __launch_bounds__(256) void k_prior_width(const WidthPair* __restrict__ pairs) {
+    __shared__ long long red[4];
+    const WidthPair P = pairs[blockIdx.x];
+    const int count = gld(P.info), code = gld(P.info + 1);
+    long long sx = 0, sy = 0;
+    if (prior_check(P.rows, count, code, P.cap, P.n, P.m, red, &sx, &sy) != 0) {
+        if (threadIdx.x == 0) gst(P.out, 0);
+        return;
+    }
+    int best = 0;
+    for (int i = threadIdx.x; i < count; i += 256) {
+        const int xl = gld(P.rows + 4 * (size_t)i + 1), yl = gld(P.rows + 4 * (size_t)i + 3);
+        const int v = xl < yl ? xl : yl;
+        best = v > best ? v : best;
+    }
+    best = block_max_int(best, red);
+    if (threadIdx.x == 0) {
+        const int rx = P.n - (int)sx, ry = P.m - (int)sy;   // the remainder row (a deletion run has min = 0)
+        const int v = rx < ry ? rx : ry;
+        best = v > best ? v : best;
+        gst(P.out, best + 1 < 3 ? 3 : best + 1);
     }
 }
 
@@ -242,5 +293,40 @@ extern "C" int svx_time_prior(svx_ctx* ctx, const svx_pair* pairs, const svx_fra
     hipLaunchKernelGGL(k_time_prior, dim3(n_pairs), dim3(256), 0, st, reinterpret_cast<const TimePair*>(dev),
                        (long long)window, (long long)lag);
     SVX_LAUNCH_CHECK(ctx, "k_time_prior");
+    return SVX_OK;
+}
+
+extern "C" int svx_prior_width(svx_ctx* ctx, const svx_pair* pairs, const svx_prior* priors, int n_pairs, int32_t* width) {
+    if (!ctx) return svx_fail(nullptr, SVX_ERR_ARG, "svx_prior_width: ctx is NULL");
+    NEED(ctx, n_pairs >= 0, "svx_prior_width: negative n_pairs");
+    NEED(ctx, n_pairs == 0 || (pairs && priors && width), "svx_prior_width: null argument");
+    if (n_pairs == 0) return SVX_OK;
+    for (int p = 0; p < n_pairs; p++) {
+        const svx_prior& q = priors[p];
+        NEED(ctx, pairs[p].n >= 0 && pairs[p].m >= 0, "svx_prior_width: pair %d: sizes n=%d m=%d", p, pairs[p].n, pairs[p].m);
+        NEED(ctx, q.cap >= 0, "svx_prior_width: pair %d: prior cap %d", p, q.cap);
+        NEED(ctx, q.info && (q.rows || q.cap == 0), "svx_prior_width: pair %d: null prior buffer", p);
+    }
+    SVX_HIP(ctx, hipSetDevice(ctx->device));
+    // ---- scratch: the descriptors only, uploaded
+    const size_t b_up = ((size_t)n_pairs * sizeof(WidthPair) + 255) & ~(size_t)255;
+    char *pin, *dev;
+    int rc = svxl_scratch_begin(ctx, "svx_prior_width", b_up, b_up, &pin, &dev);
+    if (rc) return rc;
+    WidthPair* hp = reinterpret_cast<WidthPair*>(pin);
+    for (int p = 0; p < n_pairs; p++) {
+        WidthPair& r = hp[p];
+        r.rows = priors[p].rows;
+        r.info = priors[p].info;
+        r.out = width + p;
+        r.cap = priors[p].cap;
+        r.n = pairs[p].n;
+        r.m = pairs[p].m;
+        r.pad = 0;
+    }
+    rc = svxl_scratch_upload(ctx, (size_t)n_pairs * sizeof(WidthPair));
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_prior_width, dim3(n_pairs), dim3(256), 0, ctx->stream, reinterpret_cast<const WidthPair*>(dev));
+    SVX_LAUNCH_CHECK(ctx, "k_prior_width");
     return SVX_OK;
 }

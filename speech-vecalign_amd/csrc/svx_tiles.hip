@@ -77,7 +77,10 @@ __device__ __forceinline__ void wait_vm_t() {
 }
 __device__ __forceinline__ int swz_t(int row_in_tile) { return (0x1320 >> (4 * ((row_in_tile >> 2) & 3))) & 3; }
 
-// b_offset_out of a pair, then per tile anti-diagonal s the run of tiles (I, s - I) that hold band nodes.
+// b_offset_out of a pair, then per tile anti-diagonal s the run of tiles (I, s - I) that hold band nodes.  Everything
+// comes from the level's search path: the straight line, or the path of a prior (SVX_SEARCH_AROUND_WIDE).  The run is
+// the hull of the band tiles of the diagonal; the band rows of consecutive node diagonals overlap, so it has no holes.
+// A pair that has failed by now (a prior the ingest refused, a path error) gets no tiles and takes no ticket.
 // Node (x, y) is in the band iff 0 <= y - bo[x + y] < B and 0 <= x <= xs, 0 <= y <= ys.
 __global__ __launch_bounds__(256) void k_tile_ranges(const SvxPairDev* __restrict__ pairs, int W, int B) {
     const SvxPairDev& P = pairs[blockIdx.x];
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(256) void k_tile_ranges(const SvxPairDev* __restric
             P.t_pref[s] = run;
             run += P.t_cnt[s];
         }
-        P.t_pref[P.t_nd] = run > P.t_cap ? 0 : run;  // (cannot exceed the capacity the planner derived from the same geometry)
+        P.t_pref[P.t_nd] = run > P.t_cap ? 0 : run;  // (cannot exceed the capacity plan_half derives for any unit-step path; the guard stays)
         if (run > P.t_cap) *P.status = SVX_ERR_ARG;
     }
 }

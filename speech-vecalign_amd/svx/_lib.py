@@ -11,7 +11,7 @@ SVX_F32, SVX_F16, SVX_BF16 = 0, 1, 2
 SVX_MAX_TYPES = 128
 SVX_MAX_LEVELS = 16
 SVX_MARGIN_RATIO, SVX_MARGIN_DISTANCE, SVX_MARGIN_ABSOLUTE = 0, 1, 2
-SVX_SEARCH_COARSE_TO_FINE, SVX_SEARCH_STRAIGHT, SVX_SEARCH_AROUND = 0, 1, 2
+SVX_SEARCH_COARSE_TO_FINE, SVX_SEARCH_STRAIGHT, SVX_SEARCH_AROUND, SVX_SEARCH_AROUND_WIDE = 0, 1, 2, 3
 
 SVX_OK, SVX_ERR_ARG, SVX_ERR_OVERLAPS, SVX_ERR_HIP, SVX_ERR_TRACEBACK = 0, 1, 2, 3, 4
 SVX_ERR_NOMEM, SVX_ERR_EXTEND, SVX_ERR_PATH, SVX_ERR_BP = 5, 6, 7, 8
@@ -71,7 +71,7 @@ class Frames(ctypes.Structure):
 
 
 class Prior(ctypes.Structure):
-    """svx_prior: device rows [cap][4] and info [2] of a prior alignment (svx_align_around, svx_time_prior)."""
+    """svx_prior: device rows [cap][4] and info [2] of a prior alignment (svx_align_around, svx_time_prior, svx_prior_width)."""
     _fields_ = [("rows", c_vp), ("info", c_vp), ("cap", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
@@ -133,6 +133,7 @@ _SIGS = {
     "svx_align_batch": (c_int, [c_vp, ctypes.POINTER(AlignParams), ctypes.POINTER(Pair), c_int]),
     "svx_align_around": (c_int, [c_vp, ctypes.POINTER(AlignParams), ctypes.POINTER(Pair), ctypes.POINTER(Prior), c_int]),
     "svx_time_prior": (c_int, [c_vp, ctypes.POINTER(Pair), ctypes.POINTER(Frames), c_int, c_i64, c_i64, ctypes.POINTER(Prior)]),
+    "svx_prior_width": (c_int, [c_vp, ctypes.POINTER(Pair), ctypes.POINTER(Prior), c_int, c_vp]),
     "svx_alignment_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), c_int, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "svx_concat_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), ctypes.POINTER(Frames), c_int, ctypes.POINTER(ConcatParams), c_i64,
                                 c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),

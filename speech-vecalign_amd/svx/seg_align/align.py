@@ -69,7 +69,7 @@ def parse_args(argv=None):
                    help="search region: ref = the reference's coarse-to-fine recursion (default); band = Sakoe-Chiba band of "
                         "--band cells around the straight diagonal; dense = every cell of the lattice (include/svx.h: SVX_SEARCH_STRAIGHT); "
                         "around = the reference-mode band around a prior alignment, without the pyramid (SVX_SEARCH_AROUND; "
-                        "needs --prior_dir or --prior time)")
+                        "needs --prior_dir or --prior time; --prior_band sets another band)")
     p.add_argument("--prior_dir", type=str, default=None,
                    help="--mode around: alignment files {prior_dir}/{src}-{tgt}/{s}-{t}.txt in this job's output format; a pair "
                         "without one is dropped with a warning")
@@ -78,6 +78,11 @@ def parse_args(argv=None):
     p.add_argument("--prior_window", type=float, default=30.0, help="--prior time: window length, seconds")
     p.add_argument("--prior_lag", type=float, default=0.0, help="--prior time: delay of the target side, seconds (may be negative)")
     p.add_argument("--band", type=int, default=2048, help="--mode band: cells per diagonal (2 * width_over2)")
+    p.add_argument("--prior_band", type=int, default=None,
+                   help="--mode around: cells per diagonal around the prior (2 * width_over2; even, at least 6) instead of the "
+                        "reference-mode band; above 64 cells the wide-band tile sweep runs around the prior (SVX_SEARCH_AROUND_WIDE). "
+                        "One number per run: results do not depend on batches or shards.  The pairs whose prior needs a wider band "
+                        "to be covered (svx_prior_width) are counted in the log")
     p.add_argument("--batch_size", type=int, default=32, help="document pairs per device pass")
     p.add_argument("--io_threads", type=int, default=None, help="host threads that parse / read ahead of the GPU (default: the CPU count, at most 32)")
     p.add_argument("--seed", type=int, default=None, help="derive one sampling stream per pair from (seed, pair index)")
@@ -111,8 +116,10 @@ def parse_args(argv=None):
             p.error("--mode around takes exactly one of --prior_dir and --prior time")
         if args.prior == "time" and not args.prior_window * PRIOR_SAMPLE_RATE >= 1:
             p.error("--prior_window must be at least one sample")
-    elif args.prior_dir is not None or args.prior is not None:
-        p.error("--prior_dir / --prior need --mode around")
+        if args.prior_band is not None and (args.prior_band < 6 or args.prior_band % 2 != 0):
+            p.error("--prior_band must be even and at least 6")
+    elif args.prior_dir is not None or args.prior is not None or args.prior_band is not None:
+        p.error("--prior_dir / --prior / --prior_band need --mode around")
     if args.concat_max_num is not None and not 1 <= args.concat_max_num <= 8:
         p.error("--concat_max_num must be 1 .. 8")
     if args.min_dur is not None and args.min_dur < 0:
@@ -397,6 +404,8 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
     def finish(job):
         chunk, pb, ev, held = job
         ev.synchronize()
+        if getattr(pb, "h_widths", None) is not None:   # --prior_band: priors whose blocks the band in use does not cover
+            uncovered[0] += int((pb.h_widths.numpy() > pb.width_over2).sum())
         info, align, scores, _, offs = pb.raw_results()
         if margin is not None:
             margin.collect(chunk, pb, info, align, offs)
@@ -410,6 +419,7 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
         return writes, (pb, held)  # (the pinned result buffers stay alive until the writers are done)
 
     pending_job, pending_writes = None, deque()
+    uncovered = [0]
     bar = my_tqdm(total=len(todo))
     try:
         submit_more()
@@ -438,6 +448,8 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
                 w2, search = width_over2, "coarse_to_fine"
             elif mode == "band":
                 w2, search = max(3, (args.band + 1) // 2), "straight"
+            elif mode == "around" and getattr(args, "prior_band", None) is not None:  # an explicit band around the prior
+                w2, search = args.prior_band // 2, "around_wide"
             elif mode == "around":  # the reference-mode band around a prior, no pyramid
                 w2, search = width_over2, "around"
             else:  # dense: the band covers the lattice (width_over2 > max(N, M))
@@ -450,6 +462,8 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
                                priors=priors)
             if time_prior:
                 pb.time_prior(int(round(args.prior_window * PRIOR_SAMPLE_RATE)), int(round(args.prior_lag * PRIOR_SAMPLE_RATE)))
+            if search == "around_wide":
+                pb.prior_width_async()   # (read back with the results: fetch_async)
             pb.run()
             if margin is not None:
                 margin.gather(pb)
@@ -489,7 +503,10 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
         out_pool.close()
         io_pool.join()
         out_pool.join()
+    if getattr(args, "prior_band", None) is not None:
+        logger.info(f"--prior_band {args.prior_band}: {uncovered[0]} of {len(todo)} pairs have a covering band above the band in use")
     if stats is not None:
+        stats["uncovered_priors"] = uncovered[0]
         stats["pairs"] = len(todo)
         stats["io_threads"] = nthr
 

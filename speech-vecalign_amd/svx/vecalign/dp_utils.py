@@ -94,6 +94,30 @@ def prior_rows_from_alignments(alignments):
     return rows
 
 
+def prior_width(rows_or_alignments, n, m):
+    """Host twin of svx_prior_width (include/svx.h): the width_over2 from which the band around a prior holds every node
+    of every block of that prior -- 1 + max over the ingested rows, the remainder row included, of min(x_len, y_len),
+    never less than 3; 0 for a prior the ingest of svx_align_around would fail.
+    rows_or_alignments: int [r, 4] rows (x_start, x_len, y_start, y_len), of which the lengths are read, or a list of
+    alignments [(x ids, y ids), ...] as read_alignments returns."""
+    if isinstance(rows_or_alignments, np.ndarray):
+        rows = rows_or_alignments
+    elif len(rows_or_alignments) and isinstance(rows_or_alignments[0], tuple) and len(rows_or_alignments[0]) == 2:
+        rows = prior_rows_from_alignments(rows_or_alignments)
+    else:
+        rows = np.asarray(rows_or_alignments)
+    rows = np.asarray(rows, np.int64).reshape(-1, 4)
+    xl, yl = rows[:, 1], rows[:, 3]
+    if ((xl < 0) | (yl < 0) | ((xl == 0) & (yl == 0))).any():
+        return 0
+    sx, sy = int(xl.sum()), int(yl.sum())
+    if sx > n or sy > m:
+        return 0
+    best = int(np.minimum(xl, yl).max()) if len(rows) else 0
+    best = max(best, min(n - sx, m - sy))
+    return max(3, best + 1)
+
+
 def level_sizes(n, m, max_size_full_dp):
     """Sizes per depth, dp_utils.py:403-408."""
     L = _lib.load().svx_num_levels(int(n), int(m), int(max_size_full_dp))
@@ -180,15 +204,17 @@ class PreparedBatch:
         search: "coarse_to_fine" (the reference's recursion) or "straight" (band of half-width `width_over2`
         around the straight line from (0,0) to (N,M): Sakoe-Chiba / dense search, include/svx.h SVX_SEARCH_STRAIGHT;
         no pyramid, so `max_size_full_dp` is ignored), or "around": the straight search with the band laid around a prior
-        alignment instead of the straight line (svx_align_around; band of at most 64 cells).
-        priors (search="around" only): per pair one of (rows, info) device tensors (int32 [cap, 4] and [2]); another
+        alignment instead of the straight line (svx_align_around; band of at most 64 cells), or "around_wide": the same
+        with any band (SVX_SEARCH_AROUND_WIDE: above 64 cells the tile sweep of the wide straight search runs around the
+        prior's path; prior_width() gives the width that covers the prior's blocks).
+        priors (search="around" and "around_wide" only): per pair one of (rows, info) device tensors (int32 [cap, 4] and [2]); another
         PreparedBatch (its align / info slices: same pair order and sizes, read on the device when run() is called, with
         no host round trip); a host list of alignments [(x_ids, y_ids), ...] as read_alignments returns
         (prior_rows_from_alignments); or None, to be filled by time_prior() before run()."""
-        if search not in ("coarse_to_fine", "straight", "around"):
-            raise ValueError("search must be 'coarse_to_fine', 'straight' or 'around'")
-        if (priors is not None) != (search == "around"):
-            raise ValueError("priors go with search='around', and only with it")
+        if search not in ("coarse_to_fine", "straight", "around", "around_wide"):
+            raise ValueError("search must be 'coarse_to_fine', 'straight', 'around' or 'around_wide'")
+        if (priors is not None) != (search in ("around", "around_wide")):
+            raise ValueError("priors go with search='around' / 'around_wide', and only with them")
         if search != "coarse_to_fine":
             max_size_full_dp = 1 << 30  # depth 0 only: the random draws of a vecalign() call without pyramid levels
         ctx = _lib.context(device)
@@ -239,7 +265,8 @@ class PreparedBatch:
         prm.costs_sample_size = int(costs_sample_size)
         prm.num_samps_for_norm = int(num_samps_for_norm)
         prm.del_percentile_frac = float(del_percentile_frac)
-        prm.search_mode = {"straight": _lib.SVX_SEARCH_STRAIGHT, "around": _lib.SVX_SEARCH_AROUND}.get(search, _lib.SVX_SEARCH_COARSE_TO_FINE)
+        prm.search_mode = {"straight": _lib.SVX_SEARCH_STRAIGHT, "around": _lib.SVX_SEARCH_AROUND,
+                           "around_wide": _lib.SVX_SEARCH_AROUND_WIDE}.get(search, _lib.SVX_SEARCH_COARSE_TO_FINE)
         self.prm = prm
         npairs = len(self.vecs)
         self.cpairs = (_lib.Pair * npairs)()
@@ -304,7 +331,7 @@ class PreparedBatch:
             c.info = self.info.data_ptr() + 8 * i
             c.del_pen = self.del_pen.data_ptr() + 8 * _lib.SVX_MAX_LEVELS * i
         self.cpriors = None
-        if search == "around":
+        if search in ("around", "around_wide"):
             self._set_priors(priors)
 
     def _set_priors(self, priors):
@@ -349,12 +376,28 @@ class PreparedBatch:
         block per window of `window` samples, the target side shifted by `lag` samples.  Needs `frames` and priors given
         as None.  Asynchronous on the current stream; run() then reads the rows on the device."""
         if self.cpriors is None or any(o is None for o in self.prior_own):
-            raise ValueError("time_prior() needs search='around' with priors=[None, ...]")
+            raise ValueError("time_prior() needs search='around' / 'around_wide' with priors=[None, ...]")
         if self.cframes is None:
             raise ValueError("time_prior() needs the batch's frames")
         ctx = self.ctx
         ctx.use_current_stream()
         ctx.check(ctx.lib.svx_time_prior(ctx.h, self.cpairs, self.cframes, len(self.vecs), int(window), int(lag), self.cpriors))
+
+    def prior_width_async(self):
+        """svx_prior_width on the batch's priors (include/svx.h): -> int32 device tensor [pairs], the width_over2 that
+        covers each pair's prior (0 for a prior the ingest would fail).  Asynchronous on the current stream."""
+        if self.cpriors is None:
+            raise ValueError("prior_width() needs search='around' or 'around_wide'")
+        ctx = self.ctx
+        ctx.use_current_stream()
+        ctx.flush()   # (a prior may be the output of a batch the pipeline still holds back)
+        self.widths = ctx.torch.empty(len(self.vecs), dtype=ctx.torch.int32, device=ctx.tdev)
+        ctx.check(ctx.lib.svx_prior_width(ctx.h, self.cpairs, self.cpriors, len(self.vecs), _p(self.widths)))
+        return self.widths
+
+    def prior_width(self):
+        """prior_width_async() read back: an int32 numpy array [pairs] (one small copy, which synchronises the stream)."""
+        return self.prior_width_async().cpu().numpy()
 
     def run(self):
         """Launch the whole pipeline for the batch (asynchronous on the current torch stream)."""
@@ -469,6 +512,9 @@ class PreparedBatch:
         self.h_out = tuple(t.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in (self.info, self.align, self.scores, self.del_pen))
         for h, d in zip(self.h_out, (self.info, self.align, self.scores, self.del_pen)):
             h.copy_(d, non_blocking=True)
+        if getattr(self, "widths", None) is not None:   # (prior_width_async(): the covering widths ride along)
+            self.h_widths = t.empty(self.widths.shape, dtype=self.widths.dtype, pin_memory=True)
+            self.h_widths.copy_(self.widths, non_blocking=True)
         if getattr(self, "rows", None) is not None:
             self.h_rows = tuple(t.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in (self.rows[5], self.rows[4]))
             for h, d in zip(self.h_rows, (self.rows[5], self.rows[4])):
