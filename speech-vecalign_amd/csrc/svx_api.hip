@@ -464,7 +464,7 @@ int svx_make_norm1(svx_ctx* ctx, float* vecs, int64_t rows, int d) {
 }
 
 int svx_downsample(svx_ctx* ctx, const float* vecs, int k, int n, int d, float* half) {
-    NEED(ctx, ctx && vecs && (half || n < 2), "svx_downsample: null argument");
+    NEED(ctx, ctx && (vecs || n < 1 || k < 1) && (half || n < 2 || k < 1), "svx_downsample: null argument");  // an empty tensor has no address
     int rc = check_dim(ctx, d);
     if (rc) return rc;
     const int h = n / 2;

@@ -1198,7 +1198,11 @@ __device__ void del_penalty_block(const float* scores, long long n, double frac,
         __syncthreads();
     }
     float res_max = red[0];
-    if (!(0.0f < res_max)) res_max = 1e-4f;  // dp_utils.py:55-57 (res_min = 0)
+    // dp_utils.py:55-57 (res_min = 0): no sample above zero makes the range [0, 0 + 1e-4], and that sum is a python
+    // float: the interpolation knots carry the double 1e-4, not the float32 nearest to it
+    const bool empty_range = !(0.0f < res_max);
+    if (empty_range) res_max = 1e-4f;
+    const double res_max_d = empty_range ? 1e-4 : (double)res_max;
     const float step = res_max / 1000.0f;
     for (int i = tid; i < 1001; i += blockDim.x) edges[i] = (i == 1000) ? res_max : (float)i * step;
     for (int i = tid; i < 1000; i += blockDim.x) cnt[i] = 0;
@@ -1229,16 +1233,16 @@ __device__ void del_penalty_block(const float* scores, long long n, double frac,
             const double cdf = run * dx;
             while (k <= 27 && cdf >= (double)k * kstep) {  // searchsorted(cdf, knot, 'left') == i
                 xs[k] = (double)k * kstep;
-                ys[k] = 0.0 + (double)i / 1000.0 * (double)res_max;
+                ys[k] = 0.0 + (double)i / 1000.0 * res_max_d;
                 k++;
             }
         }
         for (; k <= 27; k++) {  // knot above the whole cdf: searchsorted returns len(cdf)
             xs[k] = (double)k * kstep;
-            ys[k] = 0.0 + 1000.0 / 1000.0 * (double)res_max;
+            ys[k] = 0.0 + 1000.0 / 1000.0 * res_max_d;
         }
         xs[28] = 1.0;
-        ys[28] = (double)res_max;
+        ys[28] = res_max_d;
         // np.interp
         double res;
         if (frac < xs[0]) res = ys[0];

@@ -44,11 +44,13 @@ def norms(v_self, v_other, sampled_indices):
     return 1.0 - np.matmul(v_self, samp.T).mean(axis=2)
 
 
-def dense_costs(v0, v1, n0, n1):
-    """make_dense_costs (dp_core.pyx:36-77) with offsets 0: 2 (1 - <a, b>) / (1e-6 + n0 + n1) on layer 0."""
+def dense_costs(v0, v1, n0, n1, offset0=0, offset1=0):
+    """make_dense_costs (dp_core.pyx:36-77): (offset0 + 1) (offset1 + 1) 2 (1 - <a, b>) / (1e-6 + n0 + n1) on the
+    overlap layers offset0 of v0 / n0 and offset1 of v1 / n1 (the defaults: layer 0, factor 1)."""
     v0, v1 = np.asarray(v0, np.float64), np.asarray(v1, np.float64)
-    dots = np.matmul(v0[0], v1[0].T)
-    return 2.0 * (1.0 - dots) / ((1e-6 + np.asarray(n0, np.float64)[0][:, None]) + np.asarray(n1, np.float64)[0][None, :])
+    dots = np.matmul(v0[offset0], v1[offset1].T)
+    c = 2.0 * (1.0 - dots) / ((1e-6 + np.asarray(n0, np.float64)[offset0][:, None]) + np.asarray(n1, np.float64)[offset1][None, :])
+    return c * float((offset0 + 1) * (offset1 + 1))
 
 
 def score_path(xs, ys, n0, n1, v0, v1):
