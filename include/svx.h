@@ -53,8 +53,8 @@ int svx_synchronize(svx_ctx *ctx);
 const char *svx_last_error(const svx_ctx *ctx);
 const char *svx_version(void);
 /* Bytes of device scratch currently held by the context: the arena and the post-processing scratch.
- * The post-processing scratch is what svx_alignment_rows, svx_concat_rows, svx_knn_search_groups, svx_time_prior and
- * svx_prior_width work in: one grow-only device buffer of the context's own, not in the arena -- the views of svx_debug_level stay valid --,
+ * The post-processing scratch is what svx_alignment_rows, svx_concat_rows, svx_knn_search_groups, svx_time_prior,
+ * svx_prior_width, svx_band_contact and svx_align_widen work in: one grow-only device buffer of the context's own, not in the arena -- the views of svx_debug_level stay valid --,
  * shared by these calls (they are ordered on the context's stream) and filled through two pinned staging buffers
  * taken in turn, like svx_align_batch's descriptors.  It grows with 25 % slack behind one stream synchronisation and is
  * released by svx_destroy. */
@@ -499,6 +499,57 @@ int svx_time_prior(svx_ctx *ctx, const svx_pair *pairs, const svx_frames *frames
  * Asynchronous on the context's stream, no host synchronisation.  Scratch: the descriptors only, in the context's
  * post-processing scratch (svx_scratch_bytes). */
 int svx_prior_width(svx_ctx *ctx, const svx_pair *pairs, const svx_prior *priors, int n_pairs, int32_t *width);
+
+/* ---- band-edge contact and band doubling (csrc/svx_contact.hip) ------------------------------------------------
+ * Every search here is a banded DP: 2 * width_over2 cells per diagonal around a search path that something else chose (the
+ * up-sampled coarser alignment, the straight line, the caller's prior).  Where the best alignment wants to leave that band
+ * the DP returns the best path INSIDE it: a search error.  svx_band_contact reports the classical symptom -- nodes of the
+ * returned path on the outermost cells of their diagonals -- and svx_align_widen applies the classical remedy, band
+ * doubling: search again around the path just found, in twice the band, until the path clears the edge.  Widening removes
+ * search errors, not model errors: on noisy data a lower-cost path need not hold more of the true pairs,
+ * so the report is always available and the re-search is the caller's choice.
+ *
+ * svx_band_contact covers the pairs of the LAST svx_align_batch / svx_align_around call on the context -- the pairs
+ * svx_debug_level addresses, both halves of a pipelined call -- at pyramid level `level` of that call.  It calls svx_flush
+ * first and is asynchronous on the context's stream, with no host synchronisation.  It reads integers only: the level's
+ * alignment rows and their count, its new_b_offset, the level's sizes, the band B = 2 * width_over2 of that call and the
+ * pair's info.
+ *   Nodes of a level: (0, 0) and, for every alignment row in order, (x_start + x_len, y_start + y_len).
+ *   For a node (x, y): a = x + y, o = new_b_offset[a], b = y - o.  The cell just outside the band is (a - (o - 1), o - 1) on
+ *   the low side and (a - (o + B), o + B) on the high side; a side is REAL iff that cell is a lattice node of the level,
+ *   0 <= x' <= size0 and 0 <= y' <= size1.  The node's clearance is the minimum over its real sides of b (low) and
+ *   B - 1 - b (high), INT32_MAX when neither side is real: document borders never count, and in a band that covers the
+ *   whole lattice nothing touches.  A node TOUCHES iff its clearance is <= guard.
+ * out (device, [n_pairs][4] int32, 16-byte aligned): out[p] = (touch, run, clearance, nodes) = the number of touching
+ * nodes, the longest run of consecutive touching nodes, the minimum clearance over all nodes, the node count; or
+ * (-1, -1, -1, -1) for a pair whose info[1] != 0 and for a level the pair did not refine (level > L, and the dense coarsest
+ * level when L > 0).
+ * A null argument, level < 0, guard < 0 or no earlier (successful) call return SVX_ERR_ARG with text and queue nothing.
+ * One workgroup per pair; scratch (the descriptors) is the context's post-processing scratch (svx_scratch_bytes). */
+int svx_band_contact(svx_ctx *ctx, int level, int guard, int32_t *out);
+
+/* Band doubling.  SYNCHRONOUS: every round ends with a read-back of the contact report, and the entry returns with all
+ * outputs complete.
+ *   Round 0 is exactly svx_align_batch(params, pairs) when priors == NULL (SVX_SEARCH_COARSE_TO_FINE or
+ *   SVX_SEARCH_STRAIGHT) or svx_align_around(params, pairs, priors) otherwise, followed by svx_band_contact(0, guard).
+ *   Round r >= 1: the pairs that touch (touch > 0, info[1] == 0) are searched again in ONE svx_align_around call in
+ *   SVX_SEARCH_AROUND_WIDE with width_over2 = min(W0 * 2^r, max_width_over2), W0 = params->width_over2 raised to 3.  The
+ *   prior of a pair is its current result, which the library first copies into the post-processing scratch (rows up to
+ *   the count read on the device, and info), since a prior may not be the pair's own output; the results go into the
+ *   pair's own align / scores / info (and del_pen).  Every other field of svx_pair is passed unchanged, the norm_idx /
+ *   knob_idx pointers included: the depth-0 draws are the leading entries of both arrays in either layout, so every round
+ *   uses the depth-0 normaliser and penalty draws of round 0.  svx_band_contact(0, guard) follows.
+ *   It stops when nothing touches, after max_rounds rounds, or when the width has reached max_width_over2.
+ * report (HOST, [n_pairs][4]): (rounds run for this pair, its final width_over2, touch after round 0, touch after its last
+ * round); touch is -1 for a failed pair.  max_rounds = 0 is round 0 plus the report.
+ * Outputs and report equal, bit for bit, those of that sequence of public calls.  A non-zero return of an internal call
+ * is returned as is.  Afterwards svx_debug_level, svx_band_contact and the stage timers see the LAST internal call: with
+ * r >= 1 that is the batch of the pairs searched again in the last round, in their order.
+ * A null argument, a negative field of wp, or max_width_over2 < W0 return SVX_ERR_ARG with text and queue nothing.
+ * svx_pair, svx_align_params and svx_prior are what the other entries take. */
+typedef struct svx_widen_params { int32_t guard, max_width_over2, max_rounds, reserved; } svx_widen_params;
+int svx_align_widen(svx_ctx *ctx, const svx_align_params *params, const svx_pair *pairs, const svx_prior *priors /* nullable */,
+                    int n_pairs, const svx_widen_params *wp, int32_t *report /* HOST [n_pairs][4] */);
 
 /* Per-level intermediates of the LAST svx_align_batch call on this context -- the entries of the `stack` the reference
  * returns (dp_utils.py:412-537) -- as device pointers into the context's scratch arena (valid until the next call;

@@ -98,6 +98,7 @@ struct svx_ctx_ext : svx_ctx {
     hipEvent_t side_fork, side_join;
     bool side_ready;
     int last_ntypes, last_band;  // of the last svx_align_batch call (svx_debug_level)
+    bool last_ok;                // that call planned and launched everything: its descriptors hold device pointers (svx_band_contact)
 };
 
 static inline svx_ctx_ext* X(svx_ctx* c) { return static_cast<svx_ctx_ext*>(c); }
@@ -161,6 +162,7 @@ int svx_create(int device_id, svx_ctx** out) {
     c->ev_next = 0;
     c->last_ntypes = 0;
     c->last_band = 0;
+    c->last_ok = false;
     c->side_ready = false;
     *out = c;
     return SVX_OK;
@@ -600,6 +602,19 @@ extern "C" int svx_debug_level(svx_ctx* ctx, int pair, int level, svx_level_view
         out->v1_l0 = Lv.P[1];
     }
     return SVX_OK;
+}
+
+// The host mirrors of the last batch's descriptors, first half then second (svx_contact.hip); false when there is none.
+bool svxl_last_batch(svx_ctx* ctx, const SvxPairDev** host, int* n_pairs, int* band) {
+    svx_ctx_ext* cx = X(ctx);
+    if (!cx->last_ok) return false;
+    host[0] = cx->half[0].host.data();
+    n_pairs[0] = cx->half[0].n_pairs;
+    const bool two = cx->last_split > 0;
+    host[1] = two ? cx->half[1].host.data() : nullptr;
+    n_pairs[1] = two ? cx->half[1].n_pairs : 0;
+    *band = cx->last_band;
+    return true;
 }
 
 // ------------------------------------------------------------------------------ plan of one half
@@ -1201,6 +1216,7 @@ static int align_impl(svx_ctx* ctx, const svx_align_params* prm, const svx_pair*
     // (shape: the two LDS-resident ones for the sets they take, else the general one; every set make_types accepts)
     if (bp.tiles) NEED(ctx, bp.tfinal.n >= 1 && svxl_band_tiles_shape(bp.tfinal) >= 0, "wide straight band: no tile shape takes these %d alignment types", bp.tfinal.n);
     if ((rc = ensure_streams(ctx))) return rc;
+    cx->last_ok = false;   // (until this call has replaced the descriptors of the one before)
     for (int i = 0; i < S_COUNT; i++) { cx->ms[i] = 0.0; cx->launches[i] = 0; }
     for (auto& r : cx->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     cx->recs.clear();
@@ -1237,6 +1253,7 @@ static int align_impl(svx_ctx* ctx, const svx_align_params* prm, const svx_pair*
     }
     cx->last_ntypes = bp.tfinal.n;
     cx->last_band = bp.B;
+    cx->last_ok = true;
     const auto t_done = std::chrono::steady_clock::now();
     cx->ms[S_HOST_PLAN] = plan_ms;
     cx->ms[S_HOST_LAUNCH] = std::chrono::duration<double, std::milli>(t_done - t_enter).count() - plan_ms;

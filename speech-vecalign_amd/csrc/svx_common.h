@@ -253,7 +253,8 @@ struct svx_ctx {
     // without waiting for the upload of the call before.  Its users, ordered on the context's stream, each lay out the
     // whole buffer anew: svx_alignment_rows and svx_concat_rows (svx_alignrows.hip: descriptors, chunk table, counts,
     // offsets, compacted rows), svx_knn_search_groups (svx_groupsearch.hip: offsets, workgroup table) and svx_time_prior
-    // (svx_prior.hip: descriptors, prefix counts).  They go through svxl_scratch_begin / svxl_scratch_upload only.
+    // (svx_prior.hip: descriptors, prefix counts), svx_band_contact and svx_align_widen (svx_contact.hip: descriptors, the
+    // report rows, the staged priors of a round).  They go through svxl_scratch_begin / svxl_scratch_upload only.
     char* post_buf;
     size_t post_bytes;        // counted in svx_scratch_bytes
     char* post_pin[2];
@@ -336,3 +337,5 @@ int svxl_del_penalty(svx_ctx*, const float* scores, int64_t n, double frac, doub
 int svxl_del_penalty_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int max_levels, double frac);
 // prior alignments (svx_prior.hip)
 int svxl_prior_ingest_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs);
+// band contact (svx_contact.hip reads the descriptors of the last batch: svx_api.hip)
+bool svxl_last_batch(svx_ctx*, const SvxPairDev** host, int* n_pairs, int* band);

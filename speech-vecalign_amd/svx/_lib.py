@@ -75,6 +75,12 @@ class Prior(ctypes.Structure):
     _fields_ = [("rows", c_vp), ("info", c_vp), ("cap", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class WidenParams(ctypes.Structure):
+    """svx_widen_params: band doubling (svx_align_widen)."""
+    _fields_ = [("guard", ctypes.c_int32), ("max_width_over2", ctypes.c_int32), ("max_rounds", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class ConcatParams(ctypes.Structure):
     """svx_concat_params (include/svx.h)."""
     _fields_ = [
@@ -134,6 +140,9 @@ _SIGS = {
     "svx_align_around": (c_int, [c_vp, ctypes.POINTER(AlignParams), ctypes.POINTER(Pair), ctypes.POINTER(Prior), c_int]),
     "svx_time_prior": (c_int, [c_vp, ctypes.POINTER(Pair), ctypes.POINTER(Frames), c_int, c_i64, c_i64, ctypes.POINTER(Prior)]),
     "svx_prior_width": (c_int, [c_vp, ctypes.POINTER(Pair), ctypes.POINTER(Prior), c_int, c_vp]),
+    "svx_band_contact": (c_int, [c_vp, c_int, c_int, c_vp]),
+    "svx_align_widen": (c_int, [c_vp, ctypes.POINTER(AlignParams), ctypes.POINTER(Pair), ctypes.POINTER(Prior), c_int,
+                                ctypes.POINTER(WidenParams), c_vp]),
     "svx_alignment_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), c_int, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "svx_concat_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), ctypes.POINTER(Frames), c_int, ctypes.POINTER(ConcatParams), c_i64,
                                 c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),

@@ -25,6 +25,11 @@ is NOT part of the chain.  With --margin_dir the chain runs on the device (svx_c
 line per joined alignment whose span is still a candidate row (at most k0 x k1 segments); wider ones need the encoder and
 are only counted.  --post_dir DIR writes the chain's full output, wide lines included, as concat_aligns / filter_by_dur write
 it; that is host work on the results already fetched (filters.post_chain).
+
+--contact_tsv PATH reports, per pair, how many nodes of the returned path sit on the edge of the search band
+(svx_band_contact): the sign that the band may have cut the best alignment off.  --widen searches such pairs again around
+their own result in twice the band until the path clears the edge (svx_align_widen; --widen_rounds, --widen_max_band,
+--widen_guard).  It removes search errors, not model errors, so it is opt-in; without these flags nothing changes.
 """
 import argparse
 import dataclasses
@@ -83,6 +88,20 @@ def parse_args(argv=None):
                         "reference-mode band; above 64 cells the wide-band tile sweep runs around the prior (SVX_SEARCH_AROUND_WIDE). "
                         "One number per run: results do not depend on batches or shards.  The pairs whose prior needs a wider band "
                         "to be covered (svx_prior_width) are counted in the log")
+    p.add_argument("--contact_tsv", type=str, default=None,
+                   help="write one line per pair, 'src tgt touch run clearance nodes rounds final_band' (tab-separated): the nodes of the "
+                        "returned path on the edge of the search band, the longest run of them, the smallest distance to the edge in "
+                        "cells and the node count (svx_band_contact); a path that touches may be a search error.  With --widen: touch "
+                        "after the pair's last round, and -1 for run, clearance and nodes")
+    p.add_argument("--widen", action="store_true", default=False,
+                   help="search a pair whose path touches the band edge again around that path in twice the band, until it clears "
+                        "the edge (svx_align_widen).  Removes search errors, not model errors; meant for bands the user chose "
+                        "(--mode band, --mode around)")
+    p.add_argument("--widen_rounds", type=int, default=4, help="--widen: doublings at the most")
+    p.add_argument("--widen_max_band", type=int, default=None,
+                   help="--widen: cells per diagonal at the most (default: the band in use times 2 ** widen_rounds)")
+    p.add_argument("--widen_guard", type=int, default=0,
+                   help="--widen / --contact_tsv: a node touches when it is at most this many cells from the edge")
     p.add_argument("--batch_size", type=int, default=32, help="document pairs per device pass")
     p.add_argument("--io_threads", type=int, default=None, help="host threads that parse / read ahead of the GPU (default: the CPU count, at most 32)")
     p.add_argument("--seed", type=int, default=None, help="derive one sampling stream per pair from (seed, pair index)")
@@ -120,6 +139,10 @@ def parse_args(argv=None):
             p.error("--prior_band must be even and at least 6")
     elif args.prior_dir is not None or args.prior is not None or args.prior_band is not None:
         p.error("--prior_dir / --prior / --prior_band need --mode around")
+    if args.widen_rounds < 0 or args.widen_guard < 0:
+        p.error("--widen_rounds and --widen_guard must be >= 0")
+    if args.widen_max_band is not None and args.widen_max_band < 6:
+        p.error("--widen_max_band must be at least 6")
     if args.concat_max_num is not None and not 1 <= args.concat_max_num <= 8:
         p.error("--concat_max_num must be 1 .. 8")
     if args.min_dur is not None and args.min_dur < 0:
@@ -407,6 +430,20 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
         if getattr(pb, "h_widths", None) is not None:   # --prior_band: priors whose blocks the band in use does not cover
             uncovered[0] += int((pb.h_widths.numpy() > pb.width_over2).sum())
         info, align, scores, _, offs = pb.raw_results()
+        report = getattr(pb, "widen_report", None)
+        if report is not None:
+            widened[0] += int((report[:, 0] > 0).sum())
+            touching[0] += int((report[:, 3] > 0).sum())
+        elif getattr(pb, "h_contact", None) is not None:
+            touching[0] += int((pb.h_contact.numpy()[:, 0] > 0).sum())
+        if contact_tsv is not None:
+            for i, p in enumerate(chunk):
+                s, t = os.path.basename(p.src_seg_path), os.path.basename(p.tgt_seg_path)
+                if report is not None:
+                    vals = [int(report[i, 3]), -1, -1, -1, int(report[i, 0]), 2 * int(report[i, 1])]
+                else:
+                    vals = pb.h_contact.numpy()[i].tolist() + [0, 2 * int(pb.width_over2)]
+                contact_lines.append("\t".join([s, t] + [str(v) for v in vals]) + "\n")
         if margin is not None:
             margin.collect(chunk, pb, info, align, offs)
         writes = []
@@ -420,6 +457,10 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
 
     pending_job, pending_writes = None, deque()
     uncovered = [0]
+    widen = bool(getattr(args, "widen", False))
+    contact_tsv = getattr(args, "contact_tsv", None)
+    guard = int(getattr(args, "widen_guard", 0))
+    widened, touching, contact_lines = [0], [0], []
     bar = my_tqdm(total=len(todo))
     try:
         submit_more()
@@ -464,7 +505,15 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
                 pb.time_prior(int(round(args.prior_window * PRIOR_SAMPLE_RATE)), int(round(args.prior_lag * PRIOR_SAMPLE_RATE)))
             if search == "around_wide":
                 pb.prior_width_async()   # (read back with the results: fetch_async)
-            pb.run()
+            if widen:   # (synchronous: every round reads its contact report back)
+                max_w2 = None if getattr(args, "widen_max_band", None) is None else max(pb.width_over2, args.widen_max_band // 2)
+                pb.widen_report = pb.run_widen(guard=guard, max_width_over2=max_w2, max_rounds=args.widen_rounds)
+            else:
+                pb.run()
+                if contact_tsv is not None:
+                    contact = pb.band_contact(0, guard)
+                    pb.h_contact = torch.empty(contact.shape, dtype=contact.dtype, pin_memory=True)
+                    pb.h_contact.copy_(contact, non_blocking=True)   # (lands before the event of fetch_async)
             if margin is not None:
                 margin.gather(pb)
             ev = pb.fetch_async()
@@ -505,7 +554,15 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
         out_pool.join()
     if getattr(args, "prior_band", None) is not None:
         logger.info(f"--prior_band {args.prior_band}: {uncovered[0]} of {len(todo)} pairs have a covering band above the band in use")
+    if contact_tsv is not None:
+        shard = "" if getattr(args, "n_shard", 1) <= 1 else f".{args.rank}"   # (one file per rank: the ranks do not communicate)
+        _write_text(contact_tsv + shard, "".join(contact_lines))
+    if widen or contact_tsv is not None:
+        logger.info(f"band contact: {touching[0]} of {len(todo)} pairs touch the edge of their final band"
+                    + (f", {widened[0]} were searched again in a wider band" if widen else ""))
     if stats is not None:
+        stats["widened"] = widened[0]
+        stats["still_touching"] = touching[0]
         stats["uncovered_priors"] = uncovered[0]
         stats["pairs"] = len(todo)
         stats["io_threads"] = nthr

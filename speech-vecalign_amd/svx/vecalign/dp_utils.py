@@ -413,6 +413,35 @@ class PreparedBatch:
         finally:   # a call that fails half way may already have queued work that reads this batch
             ctx.hold(self)
 
+    def band_contact(self, level=0, guard=0):
+        """svx_band_contact for the last run() on the context (include/svx.h): -> int32 device tensor [pairs, 4] =
+        (touching nodes, longest run of them, minimum clearance in cells, nodes) per pair, -1 in all four for a failed
+        pair or a level the pair did not refine.  Asynchronous on the current stream."""
+        ctx = self.ctx
+        ctx.use_current_stream()
+        out = ctx.torch.empty((len(self.vecs), 4), dtype=ctx.torch.int32, device=ctx.tdev)
+        ctx.check(ctx.lib.svx_band_contact(ctx.h, int(level), int(guard), _p(out)))
+        return out
+
+    def run_widen(self, guard=0, max_width_over2=None, max_rounds=4):
+        """run() followed by band doubling (svx_align_widen, include/svx.h): pairs whose path touches the band edge are
+        searched again around that path in twice the band, up to `max_rounds` times and `max_width_over2` (default:
+        width_over2 * 2 ** max_rounds).  Synchronous.  -> int32 numpy array [pairs, 4] = (rounds run, final width_over2,
+        touching nodes after round 0, touching nodes after the last round; -1 for a failed pair)."""
+        ctx = self.ctx
+        ctx.use_current_stream()
+        self.rows = self.h_rows = None
+        wp = _lib.WidenParams()
+        wp.guard, wp.max_rounds = int(guard), int(max_rounds)
+        wp.max_width_over2 = min(int(self.width_over2) << min(24, max(0, int(max_rounds))), 1 << 30) if max_width_over2 is None else int(max_width_over2)
+        report = np.zeros((len(self.vecs), 4), np.int32)
+        try:
+            ctx.check(ctx.lib.svx_align_widen(ctx.h, ctypes.byref(self.prm), self.cpairs, getattr(self, "cpriors", None),
+                                              len(self.vecs), ctypes.byref(wp), ctypes.c_void_p(report.ctypes.data)))
+        finally:   # (as run(): a call that fails half way may have queued work that reads this batch)
+            ctx.hold(self)
+        return report
+
     def flush(self):
         """With the context's pipeline on (Context.set_pipeline): launch what run() held back and order it in front of
         whatever follows on the current stream."""
