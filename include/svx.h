@@ -108,7 +108,18 @@ int svx_compute_norms(svx_ctx *ctx, const float *vecs0, int k0, int n0, const fl
  * scores [n] float32 -> *del_penalty (device double). */
 int svx_del_penalty(svx_ctx *ctx, const float *scores, int64_t n, double frac, double *del_penalty);
 
-/* dense_traceback(bp) -> alignments                                            dp_utils.py:146-174
+/* The counting sort in front of the sampled scores (the samples of dp_utils.py:301-308, grouped by source row so that
+ * the scoring pass reads every source row once).  kx, ky [kn] int32 sample rows on the two sides, clamped to [0, n) and
+ * [0, m); kstart [n + 1]: kstart[x] = samples with a clamped source row below x, kstart[n] = kn; korder [kn]: the sample
+ * ids 0..kn-1 grouped by clamped source row (the order inside one row is unspecified); kys [kn]: kys[p] = clamped
+ * ky[korder[p]].  One workgroup; the same device code as svx_align_batch runs per (pair, level).  The scatter is staged
+ * in LDS while (n + 1 + kn) * 4 bytes fit SVX_KNOB_SORT_STAGE_LDS and goes straight to memory otherwise; n is limited
+ * by the LDS histogram ((n + 1) * 4 <= 150 KB), kn >= 0. */
+#define SVX_KNOB_SORT_STAGE_LDS (150 * 1024)
+int svx_knob_sort(svx_ctx *ctx, const int32_t *kx, const int32_t *ky, int kn, int n, int m, int32_t *korder,
+                  int32_t *kys, int32_t *kstart);
+
+/* dense_traceback(bp) -> alignments                                           dp_utils.py:146-174
  * bp [s0+1][s1+1]; align [s0+s1][4] int32 rows (x_start, x_len, y_start, y_len) in document
  * order; *count = number of rows, or -SVX_ERR_* on failure.
  * SVX_ERR_BP: a value other than 0 / 1 / 2 at a node of the walk, or a move that would leave the lattice (0 or 2 at

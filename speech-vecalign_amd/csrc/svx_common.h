@@ -301,6 +301,7 @@ int svxl_score_path(svx_ctx*, const int* xx, const int* yy, int64_t n, const flo
                     const float* v1, int rows1, const float* v2, int rows2, int d, float* out);
 int svxl_knob_scores(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int max_levels, int max_kn, int max_n0, int dtype, int d,
                      int part);
+int svxl_knob_sort(svx_ctx*, const int* kx, const int* ky, int kn, int n, int m, int* korder, int* kys, int* kstart);
 int svxl_dense_costs(svx_ctx*, const float* v0, int s0, const float* v1, int s1, int d, const float* n0,
                      const float* n1, int mul0, int mul1, float* costs);
 int svxl_dense_costs_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int max_s0, int max_s1, int dtype, int d);

@@ -253,55 +253,98 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned n);  // defi
 // korder = sample ids grouped by x, kstart[x] = first position of row x.  max and histogram do not
 // care about sample order, so the scoring kernel may visit the samples row by row and read every
 // source row once instead of once per sample.
-__global__ __launch_bounds__(256) void k_knob_sort(const SvxPairDev* __restrict__ pairs) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int part[256];
-    const SvxPairDev& P = pairs[blockIdx.y];
-    const int level = blockIdx.x;
-    if (level > P.L) return;
-    if (P.L >= 1 && level == P.L) return;  // the coarsest level's samples are scored unsorted (k_knob_from_dots)
-    const SvxLevel& Lv = P.lev[level];
-    const int n = Lv.n[0], kn = Lv.kn, tid = threadIdx.x;
-    int* cnt = reinterpret_cast<int*>(smem);  // [n]
-    for (int i = tid; i < n; i += 256) cnt[i] = 0;
+//
+// The scatter is staged in LDS when the workgroup's dynamic LDS (`lds_bytes`) holds cnt[n + 1] and ord[kn]: sample ids
+// go to ord[pos], and after a barrier korder and kys leave position by position, as full lines (kys gathers ky, an
+// 80 KB array that sits in L2).  Scattered straight to memory, the 4-byte stores of a thousand workgroups in flight
+// leave L2 as one 32-byte sector each: 5.05 MB written per pair for 0.7 MB of lists.  A level too long for that takes the
+// direct scatter in the same workgroup.  The order inside one source row is the arrival order of the atomics either way.
+template <int NT>
+__device__ __forceinline__ void knob_sort_block(const int* __restrict__ kx, const int* __restrict__ ky, int kn, int n, int m,
+                                                int* __restrict__ korder, int* __restrict__ kys, int* __restrict__ kstart,
+                                                int* cnt, int* part, size_t lds_bytes) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool staged = ((size_t)n + 1 + (size_t)kn) * sizeof(int) <= lds_bytes;  // uniform for the workgroup
+    int* ord = cnt + n + 1;  // [kn], staged way only
+    for (int i = tid; i < n; i += NT) cnt[i] = 0;
     __syncthreads();
-    for (int i = tid; i < kn; i += 256) {
-        int x = Lv.kx[i];
+    for (int i = tid; i < kn; i += NT) {
+        int x = kx[i];
         x = x < 0 ? 0 : (x >= n ? n - 1 : x);
         atomicAdd(&cnt[x], 1);
     }
     __syncthreads();
     // exclusive scan: each thread owns a contiguous slice
-    const int per = (n + 255) / 256;
-    const int lo = tid * per, hi = (lo + per) < n ? (lo + per) : n;
+    const int per = (n + NT - 1) / NT;
+    const int lo = tid * per < n ? tid * per : n, hi = (lo + per) < n ? (lo + per) : n;
     int sum = 0;
     for (int i = lo; i < hi; i++) sum += cnt[i];
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int i = 0; i < 256; i++) { const int v = part[i]; part[i] = run; run += v; }
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
     }
+    if (lane == 63) part[wave] = inc;
     __syncthreads();
-    int run = part[tid];
+    int run = inc - sum;
+    for (int w = 0; w < wave; w++) run += part[w];
     for (int i = lo; i < hi; i++) {
         const int v = cnt[i];
         cnt[i] = run;  // becomes the scatter cursor
-        Lv.kstart[i] = run;
+        kstart[i] = run;
         run += v;
     }
-    if (tid == 0) Lv.kstart[n] = kn;
+    if (tid == 0) kstart[n] = kn;
     __syncthreads();
-    for (int i = tid; i < kn; i += 256) {
-        int x = Lv.kx[i];
+    if (staged) {
+        for (int i = tid; i < kn; i += NT) {
+            int x = kx[i];
+            x = x < 0 ? 0 : (x >= n ? n - 1 : x);
+            ord[atomicAdd(&cnt[x], 1)] = i;
+        }
+        __syncthreads();
+        for (int p = tid; p < kn; p += NT) {
+            const int i = ord[p];
+            int y = ky[i];
+            y = y < 0 ? 0 : (y >= m ? m - 1 : y);
+            korder[p] = i;
+            kys[p] = y;
+        }
+        return;
+    }
+    for (int i = tid; i < kn; i += NT) {
+        int x = kx[i];
         x = x < 0 ? 0 : (x >= n ? n - 1 : x);
         const int pos = atomicAdd(&cnt[x], 1);
-        const int m = Lv.n[1];
-        int y = Lv.ky[i];
+        int y = ky[i];
         y = y < 0 ? 0 : (y >= m ? m - 1 : y);
-        Lv.korder[pos] = i;
-        Lv.kys[pos] = y;
+        korder[pos] = i;
+        kys[pos] = y;
     }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_knob_sort(const SvxPairDev* __restrict__ pairs, unsigned lds_bytes) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int part[NT / 64];
+    const SvxPairDev& P = pairs[blockIdx.y];
+    const int level = blockIdx.x;
+    if (level > P.L) return;
+    if (P.L >= 1 && level == P.L) return;  // the coarsest level's samples are scored unsorted (k_knob_from_dots)
+    const SvxLevel& Lv = P.lev[level];
+    knob_sort_block<NT>(Lv.kx, Lv.ky, Lv.kn, Lv.n[0], Lv.n[1], Lv.korder, Lv.kys, Lv.kstart, reinterpret_cast<int*>(smem), part,
+                        lds_bytes);
+}
+
+// svx_knob_sort: the same device code on plain arrays
+template <int NT>
+__global__ __launch_bounds__(NT) void k_knob_sort_plain(const int* __restrict__ kx, const int* __restrict__ ky, int kn, int n, int m,
+                                                        int* __restrict__ korder, int* __restrict__ kys, int* __restrict__ kstart,
+                                                        unsigned lds_bytes) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int part[NT / 64];
+    knob_sort_block<NT>(kx, ky, kn, n, m, korder, kys, kstart, reinterpret_cast<int*>(smem), part, lds_bytes);
 }
 
 // Target rows in flight per wave in k_knob_scores. Measured on the 1024-pair batch (levels >= 1, fp32): 1 -> 15.3 ms,
@@ -882,12 +925,68 @@ int svxl_knob_from_dots(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, int 
     return SVX_OK;
 }
 
+constexpr size_t KNOB_SORT_HIST_LDS = 150 * 1024;                  // the sort's histogram cnt[n + 1] must fit: else the samples are scored unsorted
+constexpr size_t KNOB_SORT_STAGE_LDS = SVX_KNOB_SORT_STAGE_LDS;     // cnt[n + 1] + ord[kn] within this: the scatter is staged in LDS
+static_assert(KNOB_SORT_STAGE_LDS >= KNOB_SORT_HIST_LDS, "a launch sized for staging must still hold the longest histogram");
+
+// Dynamic LDS of a sort launch for these (batch) maxima: room to stage if that fits the cap, else the cap, under which
+// the shorter levels of the batch still stage; never less than the histogram.
+static size_t knob_sort_lds(int max_n0, int max_kn) {
+    const size_t want = ((size_t)max_n0 + 1 + (size_t)max_kn) * sizeof(int);
+    return want < KNOB_SORT_STAGE_LDS ? want : KNOB_SORT_STAGE_LDS;
+}
+
+// Threads per sort workgroup.  Measured on the 1024-pair batch (step, median of 5 runs / `knob_sort` stage timer, which
+// includes the wait for a CU with the LDS free): 256 -> 104.70 ms / 11.8 ms, 512 -> 104.74, 1024 -> 104.71 / 19.6 ms:
+// the step does not care, and the small workgroup finds a CU with four free wave slots sooner than the large one finds
+// sixteen beside the pyramid pass.
+static int knob_sort_threads() {
+    static const int nt = [] {
+        const char* e = getenv("SVX_SORT_THREADS");  // tuning override: 256, 512 or 1024
+        const int v = e ? atoi(e) : 0;
+        return (v == 256 || v == 512 || v == 1024) ? v : 256;
+    }();
+    return nt;
+}
+
+template <int NT>
+static int knob_sort_launch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, int max_L, size_t smem) {
+    if (smem > 64 * 1024)
+        SVX_HIP(ctx, hipFuncSetAttribute((const void*)k_knob_sort<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(k_knob_sort<NT>, dim3(max_L + 1, n_pairs), dim3(NT), smem, ctx->stream, pairs, (unsigned)smem);
+    SVX_LAUNCH_CHECK(ctx, "k_knob_sort");
+    return SVX_OK;
+}
+
+template <int NT>
+static int knob_sort_plain_launch(svx_ctx* ctx, const int* kx, const int* ky, int kn, int n, int m, int* korder, int* kys,
+                                  int* kstart, size_t smem) {
+    if (smem > 64 * 1024)
+        SVX_HIP(ctx, hipFuncSetAttribute((const void*)k_knob_sort_plain<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(k_knob_sort_plain<NT>, dim3(1), dim3(NT), smem, ctx->stream, kx, ky, kn, n, m, korder, kys, kstart,
+                       (unsigned)smem);
+    SVX_LAUNCH_CHECK(ctx, "k_knob_sort_plain");
+    return SVX_OK;
+}
+
+int svxl_knob_sort(svx_ctx* ctx, const int* kx, const int* ky, int kn, int n, int m, int* korder, int* kys, int* kstart) {
+    if ((size_t)(n + 1) * sizeof(int) > KNOB_SORT_HIST_LDS)
+        return svx_fail(ctx, SVX_ERR_ARG, "knob_sort: %d source rows exceed the LDS histogram (max %d)", n,
+                        (int)(KNOB_SORT_HIST_LDS / sizeof(int)) - 1);
+    const size_t smem = knob_sort_lds(n, kn);
+    switch (knob_sort_threads()) {
+        case 256: return knob_sort_plain_launch<256>(ctx, kx, ky, kn, n, m, korder, kys, kstart, smem);
+        case 512: return knob_sort_plain_launch<512>(ctx, kx, ky, kn, n, m, korder, kys, kstart, smem);
+        default: return knob_sort_plain_launch<1024>(ctx, kx, ky, kn, n, m, korder, kys, kstart, smem);
+    }
+}
+
 // part 0: counting sort by source row; part 1: levels >= 1 (fp32 rows); part 2: level 0 (input dtype)
 int svxl_knob_scores(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, int max_L, int max_kn, int max_n0, int dtype, int d,
                      int part) {
     if (n_pairs <= 0 || max_kn <= 0) return SVX_OK;
     hipStream_t st = ctx->stream;
-    const bool unsorted = (size_t)(max_n0 + 1) * sizeof(int) > 150 * 1024;  // the sort's histogram does not fit LDS
+    const bool unsorted = (size_t)(max_n0 + 1) * sizeof(int) > KNOB_SORT_HIST_LDS;  // the sort's histogram does not fit LDS
     if (unsorted) {
         if (part == 0) return SVX_OK;
         const int nbu = (max_kn + 3) / 4 < 2048 ? (max_kn + 3) / 4 : 2048;
@@ -928,12 +1027,12 @@ int svxl_knob_scores(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, int max
         return SVX_OK;
     }
     if (part == 0) {
-        const size_t smem = (size_t)(max_n0 + 1) * sizeof(int);
-        if (smem > 64 * 1024)
-            SVX_HIP(ctx, hipFuncSetAttribute((const void*)k_knob_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL(k_knob_sort, dim3(max_L + 1, n_pairs), dim3(256), smem, st, pairs);
-        SVX_LAUNCH_CHECK(ctx, "k_knob_sort");
-        return SVX_OK;
+        const size_t smem = knob_sort_lds(max_n0, max_kn);
+        switch (knob_sort_threads()) {
+            case 256: return knob_sort_launch<256>(ctx, pairs, n_pairs, max_L, smem);
+            case 512: return knob_sort_launch<512>(ctx, pairs, n_pairs, max_L, smem);
+            default: return knob_sort_launch<1024>(ctx, pairs, n_pairs, max_L, smem);
+        }
     }
     int nb = (max_n0 + 3) / 4;  // one wave per source row
     if (nb > 1024) nb = 1024;

@@ -93,6 +93,7 @@ class ConcatParams(ctypes.Structure):
 
 
 SVX_CONCAT_MAX = 8
+SVX_KNOB_SORT_STAGE_LDS = 150 * 1024   # bytes of LDS within which svx_knob_sort stages its scatter (include/svx.h)
 
 _SIGS = {
     "svx_create": (c_int, [c_int, ctypes.POINTER(c_vp)]),
@@ -113,7 +114,8 @@ _SIGS = {
     "svx_downsample": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "svx_compute_norms": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp]),
     "svx_del_penalty": (c_int, [c_vp, c_vp, c_i64, c_f64, c_vp]),
-    "svx_dense_traceback": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    "svx_knob_sort": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "svx_dense_traceback": (c_int,[c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "svx_sparse_traceback": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "svx_search_path": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     "svx_gather_rows": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
