@@ -437,8 +437,7 @@ int svx_sparse_costs(svx_ctx* ctx, const float* vecs0, int k0, int xsize, const 
     if (rc) return rc;
     int* status = reinterpret_cast<int*>(ctx->arena);
     SVX_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int), ctx->stream));
-    rc = svxl_band_costs(ctx, vecs0, k0, xsize, vecs1, k1, ysize, d, SVX_F32, nullptr, nullptr, norms0, norms1, path, A, ty,
-                         width_over2, costs, b_offset, status);
+    rc = svxl_band_costs(ctx, vecs0, xsize, vecs1, ysize, d, norms0, norms1, path, A, ty, width_over2, costs, b_offset, status);
     if (rc) return rc;
     int hs = 0;
     SVX_HIP(ctx, hipMemcpyAsync(&hs, status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1018,14 +1017,13 @@ static void chain_segs(svx_ctx* ctx, HalfState& H, std::vector<Seg>& segs) {
     const int first_depth = H.maxL > 0 ? H.maxL - 1 : 0;
     for (int depth = first_depth; depth >= 0; depth--) {
         const SvxTypes ty = depth == 0 ? bp.tfinal : bp.t11;
-        int lim2 = 0, tamax2 = 0;
-        const bool v2 = !bp.tiles && svxl_band2_limits(ty, W, depth, dtype, d, &lim2, &tamax2);  // which band-cost kernel takes this level
+        int lim = 0, tamax = 0;  // band-cost chunks (none for the tile sweep; align_impl checked that the types have a kernel shape)
+        if (!bp.tiles) svxl_band2_limits(ty, W, depth, dtype, d, &lim, &tamax);
         const int maxA = H.max_A[depth];
         // (pairs whose source level has more alignment rows than the LDS holds take the kernel's serial path)
         const int src_rows = (H.maxL > 0 && !H.any_L0) ? maxA / 2 + 8 : maxA;
         cur.lb.push_back({maxA * 0.08 * waves + 60.0, depth == 0 ? S_PATH0 : S_PATH, [=]() {
-            return svxl_search_path_batch(ctx, h->dpairs, np, depth, maxA, src_rows, v2 ? lim2 : SVX_BC_ROWS - SVX_BC_TB,
-                                          bp.tiles ? 0 : (v2 ? tamax2 : SVX_BC_TAMAX));
+            return svxl_search_path_batch(ctx, h->dpairs, np, depth, maxA, src_rows, lim, tamax);
         }});
         cur.has_s = true;
         if (bp.tiles) {
@@ -1036,8 +1034,7 @@ static void chain_segs(svx_ctx* ctx, HalfState& H, std::vector<Seg>& segs) {
             }};
         } else {
             cur.s = {H.b_bc[depth] / 4.0e6, depth == 0 ? S_BAND_COSTS0 : S_BAND_COSTSN, [=]() {
-                return v2 ? svxl_band_costs2_batch(ctx, h->dpairs, np, depth, maxA, ty, W, dtype, d)
-                          : svxl_band_costs_batch(ctx, h->dpairs, np, depth, maxA, ty, W, dtype, d);
+                return svxl_band_costs2_batch(ctx, h->dpairs, np, depth, maxA, ty, W, dtype, d);
             }};
         }
         segs.push_back(cur);
@@ -1225,6 +1222,9 @@ static int align_impl(svx_ctx* ctx, const svx_align_params* prm, const svx_pair*
     bp.tiles = bp.straight && bp.B > 64;
     // (shape: the two LDS-resident ones for the sets they take, else the general one; every set make_types accepts)
     if (bp.tiles) NEED(ctx, bp.tfinal.n >= 1 && svxl_band_tiles_shape(bp.tfinal) >= 0, "wide straight band: no tile shape takes these %d alignment types", bp.tfinal.n);
+    // (narrow bands: the band-cost kernel's shapes; the deeper levels' single (1,1) type always has one)
+    int lim0 = 0, tamax0 = 0;
+    if (!bp.tiles) NEED(ctx, svxl_band2_limits(bp.tfinal, bp.W, 0, bp.dtype, bp.d, &lim0, &tamax0), "band costs: no kernel shape for %d alignment types", bp.tfinal.n);
     if ((rc = ensure_streams(ctx))) return rc;
     cx->last_ok = false;   // (until this call has replaced the descriptors of the one before)
     for (int i = 0; i < S_COUNT; i++) { cx->ms[i] = 0.0; cx->launches[i] = 0; }

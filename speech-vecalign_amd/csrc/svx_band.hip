@@ -1,12 +1,12 @@
-// svx_band.hip -- band ("sparse") costs of the fused pipeline, second generation.
+// svx_band.hip -- band ("sparse") costs: the fused pipeline's kernels and the per-op entry (svx_sparse_costs).
 //
 // Reference semantics: make_sparse_costs, svecalign/vecalign/dp_core.pyx:165-267 (cost formula :256-263).
 //
-// Why a second kernel.  The first one (svx_costs.hip) stages 48 rows x (kx + ky) layers per workgroup through
-// VGPRs in 128/256-byte k-slabs with two workgroup barriers per slab; with > 100 KB of LDS only one workgroup
-// fits a CU, so nothing overlaps its global loads, its LDS traffic and its epilogue (rocprofv3, round 1: 55 % of
-// the wave cycles parked on s_waitcnt / barriers, 36 % LDS bank-conflict cycles, 0.34 of HBM peak).  This one is
-// built around keeping bytes in flight:
+// The general kernel is the project's second (DESIGN.md section 5 keeps the history).  The first one staged 48 rows
+// x (kx + ky) layers per workgroup through VGPRs in 128/256-byte k-slabs with two workgroup barriers per slab; with
+// > 100 KB of LDS only one workgroup fit a CU, so nothing overlapped its global loads, its LDS traffic and its
+// epilogue (rocprofv3, round 1: 55 % of the wave cycles parked on s_waitcnt / barriers, 36 % LDS bank-conflict
+// cycles, 0.34 of HBM peak).  This one is built around keeping bytes in flight:
 //   * smaller chunks: up to 2 (ROWS - band) + 1 path points whose cells touch <= ROWS (32) consecutive rows per
 //     side, 256 threads, <= 76 KB of LDS -> two workgroups per CU, so one's prologue / epilogue hides under the
 //     other's k loop (the extra halo rows are L2 hits: neighbouring chunks run on the same XCD);
@@ -62,11 +62,6 @@ __device__ __forceinline__ float cost_formula2(float sumx, int p, int q, float n
     return (float)((((2.0 * (double)p) * (double)q) * (1.0 - (double)sumx)) / ((1e-6 + (double)n0) + (double)n1));
 }
 
-__device__ __forceinline__ unsigned xcd_remap2(unsigned id, unsigned n) {
-    const unsigned q = n / 8, r = n % 8, xcd = id % 8, k = id / 8;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-
 // one k-slab (16 bytes per lane of A and of B) into a 16 x 16 accumulator tile
 template <typename E>
 __device__ __forceinline__ void mma_slab16(f32x4_t& acc, const uint4& a, const uint4& b);
@@ -103,9 +98,10 @@ struct Band2Args {
     const float* nrm1;
     const int* path;    // [A][2]
     int A, W, T;
-    float* costs;       // [A][T][2W]
+    float* costs;       // cell (a, t, b) at a * sa + t * st + b (k_band_costs2; k_band_costs3 writes [A][T][2W] only)
+    size_t sa, st;      // pipeline [A][T][2W]: T * 2W, 2W; per-op entry [T][A][2W]: 2W, A * 2W
     int* boff;          // [A]
-    int* status;
+    int* status;        // set to SVX_ERR_PATH when the path is not a unit-step lattice path
 };
 
 // LDS image of a stage: row r (slot * ROWS + loc) holds its 64-byte slab as four 16-byte pieces; piece kg sits at
@@ -353,10 +349,10 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
             }
         }
         __syncthreads();
-        // ---- write-out: [a][type][b].  One band chunk and all types in this pass: the block is one contiguous run.
-        if (TBe == B && ntp == g.T && ((g.T * B) & 3) == 0) {
+        // ---- write-out.  [a][type][b] with one band chunk and all types in this pass: the block is one contiguous run.
+        if (TBe == B && ntp == g.T && ((g.T * B) & 3) == 0 && g.st == (size_t)B) {
             const int nv = TAe * ntp * TBe / 4;
-            float4* dst = reinterpret_cast<float4*>(g.costs + (size_t)a0 * g.T * B);
+            float4* dst = reinterpret_cast<float4*>(g.costs + (size_t)a0 * g.sa);
             const float4* srcv = reinterpret_cast<const float4*>(Fs);
             for (int i = tid; i < nv; i += B2_THREADS) dst[i] = srcv[i];
         } else {
@@ -365,30 +361,36 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
                 const int ai = idx / (ntp * TBe);
                 const int rem = idx - ai * (ntp * TBe);
                 const int tl = rem / TBe, bi = rem - tl * TBe;
-                g.costs[((size_t)(a0 + ai) * g.T + ps.t0 + tl) * B + (b0 + bi)] = Fs[idx];
+                g.costs[(size_t)(a0 + ai) * g.sa + (size_t)(ps.t0 + tl) * g.st + (b0 + bi)] = Fs[idx];
             }
         }
     }
 }
 
-// depth 0 uses the final types on the raw rows; deeper levels use (1,1) on the normalised fp32 layer 0
+// A band2 workgroup's LDS, declared in the kernel.  The stages are separate LDS objects: the compiler then knows that
+// the ds_reads of one stage never touch a stage an LDS-DMA is still filling, and does not drain the DMA queue in front
+// of them.
+#define BAND2_LDS(C, ROWS, NSLOT, S)                                           \
+    __shared__ __attribute__((aligned(1024))) char st0[C::STAGE];              \
+    __shared__ __attribute__((aligned(1024))) char st1[C::STAGE];              \
+    __shared__ __attribute__((aligned(1024))) char st2[S >= 3 ? C::STAGE : 16]; \
+    __shared__ __attribute__((aligned(1024))) char st3[S >= 4 ? C::STAGE : 16]; \
+    __shared__ __attribute__((aligned(16))) float Fs[C::FS_FLOATS];            \
+    __shared__ int spx[C::TAMAX + 1], spy[C::TAMAX + 1];                       \
+    __shared__ float snrm[NSLOT * ROWS], sinv[NSLOT * ROWS];                   \
+    __shared__ int ltx[SVX_MAX_TYPES + 2], lty[SVX_MAX_TYPES + 2];             \
+    __shared__ int tmask[C::XT];                                               \
+    __shared__ int lslot[NSLOT]
+#define BAND2_LDS_ARGS st0, st1, st2, st3, Fs, spx, spy, snrm, sinv, ltx, lty, tmask, lslot
+
+// The fused pipeline's kernel.  depth 0 uses the final types on the raw rows; deeper levels use (1,1) on the normalised
+// fp32 layer 0
 template <typename E, bool LV0, int ROWS, int NSLOT, int UPW, int S>
 __global__ __launch_bounds__(B2_THREADS) void k_band_costs2(const SvxPairDev* __restrict__ pairs, int depth, SvxTypes ty, BandPlan plan,
                                                             int W, int nchunk_b, int per_pair) {
     using C = Band2<E, ROWS, NSLOT, UPW, S>;
-    // the stages are separate LDS objects: the compiler then knows that the ds_reads of one stage never touch a
-    // stage an LDS-DMA is still filling, and does not drain the DMA queue in front of them
-    __shared__ __attribute__((aligned(1024))) char st0[C::STAGE];
-    __shared__ __attribute__((aligned(1024))) char st1[C::STAGE];
-    __shared__ __attribute__((aligned(1024))) char st2[S >= 3 ? C::STAGE : 16];
-    __shared__ __attribute__((aligned(1024))) char st3[S >= 4 ? C::STAGE : 16];
-    __shared__ __attribute__((aligned(16))) float Fs[C::FS_FLOATS];
-    __shared__ int spx[C::TAMAX + 1], spy[C::TAMAX + 1];
-    __shared__ float snrm[NSLOT * ROWS], sinv[NSLOT * ROWS];
-    __shared__ int ltx[SVX_MAX_TYPES + 2], lty[SVX_MAX_TYPES + 2];
-    __shared__ int tmask[C::XT];
-    __shared__ int lslot[NSLOT];
-    const unsigned wg = xcd_remap2(blockIdx.x, gridDim.x);
+    BAND2_LDS(C, ROWS, NSLOT, S);
+    const unsigned wg = xcd_remap(blockIdx.x, gridDim.x);
     const SvxPairDev& P = pairs[wg / per_pair];
     const int item = wg % per_pair;
     if (depth > P.L || (depth == P.L && P.L > 0)) return;  // refined levels only (or level 0 when L == 0)
@@ -412,9 +414,26 @@ __global__ __launch_bounds__(B2_THREADS) void k_band_costs2(const SvxPairDev* __
     g.W = W;
     g.T = ty.n;
     g.costs = Lv.costs;
+    g.sa = (size_t)ty.n * (2 * W);
+    g.st = (size_t)(2 * W);
     g.boff = Lv.boff;
     g.status = P.status;
-    band2_block<E, ROWS, NSLOT, UPW, S>(g, ty, plan, a0, TAe, item % nchunk_b, st0, st1, st2, st3, Fs, spx, spy, snrm, sinv, ltx, lty, tmask, lslot);
+    band2_block<E, ROWS, NSLOT, UPW, S>(g, ty, plan, a0, TAe, item % nchunk_b, BAND2_LDS_ARGS);
+}
+
+// The per-op entry's kernel (svx_sparse_costs; instantiated for its unit fp32 rows only): plain pointers, costs in the
+// reference's [T][A][2W] layout.  The path is cut into fixed chunks of lim + 1 points, lim = ROWS - min(2W, 16): such a
+// chunk advances at most lim rows per side, so its cells stay inside the ROWS staged rows (the argument of
+// svxl_band_costs2_batch's grid; no k_chunk_path needed).
+template <typename E, int ROWS, int NSLOT, int UPW, int S>
+__global__ __launch_bounds__(B2_THREADS) void k_band_costs2_op(Band2Args g, SvxTypes ty, BandPlan plan, int lim, int nchunk_b) {
+    using C = Band2<E, ROWS, NSLOT, UPW, S>;
+    BAND2_LDS(C, ROWS, NSLOT, S);
+    const unsigned wg = xcd_remap(blockIdx.x, gridDim.x);
+    const int a0 = (int)(wg / nchunk_b) * (lim + 1);
+    if (a0 >= g.A) return;
+    const int TAe = (g.A - a0) < (lim + 1) ? (g.A - a0) : (lim + 1);
+    band2_block<E, ROWS, NSLOT, UPW, S>(g, ty, plan, a0, TAe, wg % nchunk_b, BAND2_LDS_ARGS);
 }
 
 // ------------------------------------------------------------------------------ third generation (16-bit rows)
@@ -686,7 +705,7 @@ __global__ __launch_bounds__(B3_THREADS, 4) void k_band_costs3(const SvxPairDev*
     float* Fs = reinterpret_cast<float*>(ring);
     __shared__ int spx[2 * B3_ROWS], spy[2 * B3_ROWS];
     __shared__ float snrm[2 * B3_KX * B3_ROWS], sinv[2 * B3_KX * B3_ROWS];
-    const unsigned wg = xcd_remap2(blockIdx.x, gridDim.x);
+    const unsigned wg = xcd_remap(blockIdx.x, gridDim.x);
     const SvxPairDev& P = pairs[wg / per_pair];
     const int item = wg % per_pair;
     const SvxLevel& Lv = P.lev[0];
@@ -730,9 +749,11 @@ bool make_plan3(const SvxTypes& ty, BandPlan3* plan) {
     return true;
 }
 
+// SVX_BAND_V: 2 = the general kernel at level 0 too, 3 (default) = k_band_costs3 where it applies; values <= 1 mean 2
 int band_version() {
     const char* env = getenv("SVX_BAND_V");
-    return env ? atoi(env) : 3;
+    const int v = env ? atoi(env) : 3;
+    return v < 2 ? 2 : v;
 }
 
 // Passes: consecutive types are packed while they fit the per-pass limits (types and distinct overlap layers).
@@ -767,15 +788,19 @@ struct Variant {
     int rows, nslot, upw, s;
 };
 
-// Kernel shape for a type set: the smallest staging area that takes all its layers in one pass where possible.
-bool choose_variant(const SvxTypes& ty, int depth, Variant* v, BandPlan* plan) {
-    if (ty.n <= 0) return false;
+// Kernel shape for a type set: the smallest staging area that takes all its layers in one pass where possible.  An
+// empty list gets the first shape and a plan of zero passes: the workgroups validate the path, write b_offset and stop.
+// False when even the 20-slot shape needs more than B2_MAXPASS passes; the callers refuse such a set before they
+// queue anything.  What the retired first-generation kernel took is always planned: it staged every layer at once, at
+// most 18 in total (14 staging pieces of 16 bytes per thread), for at most SVX_MAX_TYPES = 128 types.  A pass over such
+// a set needs <= 18 <= 20 slots whatever types it holds, so passes only break at the 16-type limit: ceil(T / 16) <= 8
+// = B2_MAXPASS of them (tests/test_op_ref_cpu.py checks this on a restatement).
+bool choose_variant(const SvxTypes& ty, Variant* v, BandPlan* plan) {
     int kx = 0, ky = 0;
     for (int t = 0; t < ty.n; t++) {
         if (ty.x[t] > kx) kx = ty.x[t];
         if (ty.y[t] > ky) ky = ty.y[t];
     }
-    (void)depth;
     // one alignment type on one layer per side (the deeper pyramid levels, alignment_max_size 2): 64 rows per side,
     // so that a chunk holds up to 101 path points and only 1.28 x the rows it needs travel from L2
     const Variant opts[4] = {{64, 2, 1, 4}, {32, 8, 5, 3}, {32, 12, 8, 3}, {32, 20, 8, 2}};
@@ -792,8 +817,6 @@ bool choose_variant(const SvxTypes& ty, int depth, Variant* v, BandPlan* plan) {
 
 }  // namespace
 
-// Does the second-generation kernel handle this level?  (out: rows a chunk may span per side and the most path
-// points of a chunk, for k_chunk_path.)  SVX_BAND_V1=1 keeps the first-generation kernel for A/B measurements.
 // third generation: level 0, 16-bit rows of 256 / 512 / 1024 elements, <= 4 layers per side, <= 10 types
 static bool use_v3(const SvxTypes& types, int depth, int dtype, int d, BandPlan3* plan3) {
     const int nk3 = d / 32;  // 64-byte slabs of a 16-bit row
@@ -801,20 +824,45 @@ static bool use_v3(const SvxTypes& types, int depth, int dtype, int d, BandPlan3
            make_plan3(types, plan3);
 }
 
+// Chunk limits of the kernel that takes this level, for k_chunk_path: rows a chunk may advance per side and the most
+// path points of a chunk.  False when no kernel shape plans the type set (choose_variant).
 bool svxl_band2_limits(const SvxTypes& types, int W, int depth, int dtype, int d, int* lim, int* tamax) {
-    const char* env = getenv("SVX_BAND_V1");
-    if ((env && atoi(env) != 0) || band_version() <= 1) return false;
-    const char* deep = getenv("SVX_BAND_DEEP_V1");
-    if (depth > 0 && deep && atoi(deep) != 0) return false;
     Variant v;
     BandPlan plan;
     BandPlan3 plan3;
     if (use_v3(types, depth, dtype, d, &plan3)) v.rows = B3_ROWS;
-    else if (!choose_variant(types, depth, &v, &plan)) return false;
+    else if (!choose_variant(types, &v, &plan)) return false;
     const int B = 2 * W, tbe = B < B2_TB ? B : B2_TB;
     *lim = v.rows - tbe;
     *tamax = 2 * (v.rows - tbe) + 1;
     return true;
+}
+
+// CALL(leading template arguments..., ROWS, NSLOT, UPW, S) for the shape choose_variant picked
+#define BAND2_SHAPES(v, CALL, ...)                               \
+    do {                                                         \
+        if (v.nslot == 2) CALL(__VA_ARGS__, 64, 2, 1, 4);        \
+        else if (v.nslot == 8) CALL(__VA_ARGS__, 32, 8, 5, 3);   \
+        else if (v.nslot == 12) CALL(__VA_ARGS__, 32, 12, 8, 3); \
+        else CALL(__VA_ARGS__, 32, 20, 8, 2);                    \
+    } while (0)
+
+// svx_sparse_costs: unit fp32 rows [k][n][d] / [k][m][d] (the caller checked the layer counts), costs [T][A][2W]
+int svxl_band_costs(svx_ctx* ctx, const void* v0, int n, const void* v1, int m, int d, const float* nrm0, const float* nrm1,
+                    const int* path, int A, const SvxTypes& types, int W, float* costs, int* boff, int* status) {
+    Variant v;
+    BandPlan plan;
+    if (!choose_variant(types, &v, &plan)) return svx_fail(ctx, SVX_ERR_ARG, "band costs: no kernel shape for %d alignment types", types.n);
+    if (A <= 0) return SVX_OK;
+    const int B = 2 * W, lim = v.rows - (B < B2_TB ? B : B2_TB);
+    const int nca = (A + lim) / (lim + 1), ncb = (B + B2_TB - 1) / B2_TB;
+    Band2Args g{v0, v1, n, m, d, nullptr, nullptr, nrm0, nrm1, path, A, W, types.n, costs, (size_t)B, (size_t)A * B, boff, status};
+#define CALL_OP(E, ROWS, NSLOT, UPW, S) \
+    hipLaunchKernelGGL((k_band_costs2_op<E, ROWS, NSLOT, UPW, S>), dim3((unsigned)(nca * ncb)), dim3(B2_THREADS), 0, ctx->stream, g, types, plan, lim, ncb)
+    BAND2_SHAPES(v, CALL_OP, ElemF32);
+#undef CALL_OP
+    SVX_LAUNCH_CHECK(ctx, "k_band_costs2_op");
+    return SVX_OK;
 }
 
 int svxl_band_costs2_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, int depth, int max_A, const SvxTypes& types, int W,
@@ -849,7 +897,7 @@ int svxl_band_costs2_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, i
     }
     Variant v;
     BandPlan plan;
-    if (!choose_variant(types, depth, &v, &plan)) return svx_fail(ctx, SVX_ERR_ARG, "band costs: no kernel shape for %d alignment types", types.n);
+    if (!choose_variant(types, &v, &plan)) return svx_fail(ctx, SVX_ERR_ARG, "band costs: no kernel shape for %d alignment types", types.n);
     const int B = 2 * W, tbe = B < B2_TB ? B : B2_TB;
     const int lim = v.rows - tbe;
     const int nca = (max_A + lim) / (lim + 1), ncb = (B + B2_TB - 1) / B2_TB;  // a chunk holds at least lim + 1 points
@@ -858,18 +906,10 @@ int svxl_band_costs2_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, i
     hipStream_t st = ctx->stream;
 #define CALL2(E, LV0, ROWS, NSLOT, UPW, S) \
     hipLaunchKernelGGL((k_band_costs2<E, LV0, ROWS, NSLOT, UPW, S>), grid, dim3(B2_THREADS), 0, st, pairs, depth, types, plan, W, ncb, per_pair)
-#define CALL2_V(E, LV0)                                      \
-    do {                                                     \
-        if (v.nslot == 2) CALL2(E, LV0, 64, 2, 1, 4);        \
-        else if (v.nslot == 8) CALL2(E, LV0, 32, 8, 5, 3);   \
-        else if (v.nslot == 12) CALL2(E, LV0, 32, 12, 8, 3); \
-        else CALL2(E, LV0, 32, 20, 8, 2);                    \
-    } while (0)
-    if (depth > 0) CALL2_V(ElemF32, false);
-    else if (dtype == SVX_F32) CALL2_V(ElemF32, true);
-    else if (dtype == SVX_F16) CALL2_V(ElemF16, true);
-    else CALL2_V(ElemBF16, true);
-#undef CALL2_V
+    if (depth > 0) BAND2_SHAPES(v, CALL2, ElemF32, false);
+    else if (dtype == SVX_F32) BAND2_SHAPES(v, CALL2, ElemF32, true);
+    else if (dtype == SVX_F16) BAND2_SHAPES(v, CALL2, ElemF16, true);
+    else BAND2_SHAPES(v, CALL2, ElemBF16, true);
 #undef CALL2
     SVX_LAUNCH_CHECK(ctx, "k_band_costs2");
     return SVX_OK;

@@ -11,13 +11,6 @@
 #ifndef SVX_PYR_SLOTS
 #define SVX_PYR_SLOTS 32
 #endif
-// Band-cost tiling: path points per chunk, band cells per chunk, rows staged per side.
-#define SVX_BC_TA 32
-// The fused pipeline cuts the path into chunks of up to SVX_BC_TAMAX points whose extent on either side still
-// fits the SVX_BC_ROWS staged rows (k_chunk_path); the per-op entry point keeps fixed chunks of SVX_BC_TA.
-#define SVX_BC_TAMAX 64
-#define SVX_BC_TB 16
-#define SVX_BC_ROWS 48
 
 // ---- element types ---------------------------------------------------------------------
 struct ElemF32 {
@@ -169,6 +162,14 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Workgroups are dealt round-robin over the 8 XCDs (id % 8).  Remap the linear id so that each XCD owns one
+// contiguous range of work items: neighbours then share rows through the same L2 (band-cost chunks share up to 2W
+// rows per side; the workgroups of one k_knob_scores task gather from the same level).  Speed only, never correctness.
+__device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned n) {
+    const unsigned q = n / 8, r = n % 8, xcd = id % 8, k = id / 8;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+
 // ---- per-pair device descriptors of the fused pipeline (svx_align_batch) ---------------
 struct SvxLevel {
     int n[2];          // rows per side at this level
@@ -306,12 +307,9 @@ int svxl_dense_costs(svx_ctx*, const float* v0, int s0, const float* v1, int s1,
                      const float* n1, int mul0, int mul1, float* costs);
 int svxl_dense_costs_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int max_s0, int max_s1, int dtype, int d);
 int svxl_knob_from_dots(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int max_kn);
-int svxl_band_costs(svx_ctx*, const void* v0, int k0, int n, const void* v1, int k1, int m, int d, int dtype,
-                    const float* inv0, const float* inv1, const float* nrm0, const float* nrm1, const int* path,
-                    int A, const SvxTypes& types, int W, float* costs, int* boff, int* status);
-int svxl_band_costs_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int depth, int max_A, const SvxTypes& types,
-                          int W, int dtype, int d);
-// costs, second-generation band kernel of the fused pipeline (svx_band.hip)
+// band costs (svx_band.hip): the per-op entry, then the fused pipeline's chunk limits and launcher
+int svxl_band_costs(svx_ctx*, const void* v0, int n, const void* v1, int m, int d, const float* nrm0, const float* nrm1,
+                    const int* path, int A, const SvxTypes& types, int W, float* costs, int* boff, int* status);
 bool svxl_band2_limits(const SvxTypes& types, int W, int depth, int dtype, int d, int* lim, int* tamax);
 int svxl_band_costs2_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int depth, int max_A, const SvxTypes& types, int W,
                            int dtype, int d);

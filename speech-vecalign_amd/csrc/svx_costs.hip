@@ -1,22 +1,14 @@
-// svx_costs.hip -- similarity / cost kernels (MFMA): coarse dense costs, band ("sparse") costs
-// along the search path, and the sampled path scores that feed the deletion-penalty estimate.
+// svx_costs.hip -- similarity / cost kernels: coarse dense costs (MFMA) and the sampled path scores
+// that feed the deletion-penalty estimate.  (Band costs along the search path: svx_band.hip.)
 //
 // Reference semantics (paths relative to the reference repository):
 //   make_dense_costs   svecalign/vecalign/dp_core.pyx:36-77
 //   score_path         svecalign/vecalign/dp_core.pyx:143-161
-//   make_sparse_costs  svecalign/vecalign/dp_core.pyx:165-267
 //
 // Design.  A cost is 2pq(1 - <u,v>)/(1e-6 + n0 + n1) with u,v unit rows.  The rows stay in their
 // storage type (bf16 / fp16 / fp32, exactly representable products, fp32 accumulate in the matrix
 // cores) and the unit-normalisation is applied as the two scalars 1/(||u||+1e-5), 1/(||v||+1e-5)
 // in the epilogue, so normalised copies of level 0 are never written to HBM.
-//
-// Band kernel: one workgroup owns SVX_BC_TA consecutive path points x SVX_BC_TB band cells.  The
-// cells of that chunk only touch <= 47 consecutive rows per side, so the workgroup stages those
-// rows (all overlap layers) through LDS in 128-byte k-slabs and evaluates every needed
-// (type, x-row, y-row) product as 16x16 MFMA tiles; the epilogue picks the band cells out of the
-// accumulators, applies the cost formula in double like the reference, stages the [type][a][b]
-// block in LDS and writes it out coalesced.
 #include <stdlib.h>
 
 #include "svx_common.h"
@@ -246,8 +238,6 @@ template <typename E, int NCH>
 __global__ __launch_bounds__(256) void k_score_path(ScoreArgs g) {
     score_block<E, NCH>(g, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), (int64_t)gridDim.x * 4);
 }
-
-__device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned n);  // defined with the band kernels below
 
 // Counting sort of one level's knob samples by source row (one workgroup per (level, pair)):
 // korder = sample ids grouped by x, kstart[x] = first position of row x.  max and histogram do not
@@ -489,378 +479,6 @@ __global__ __launch_bounds__(256) void k_knob_from_dots(const SvxPairDev* __rest
     }
 }
 
-// ------------------------------------------------------------------------------ band costs
-constexpr int TA = SVX_BC_TA, TAMAX = SVX_BC_TAMAX, TB = SVX_BC_TB, ROWS = SVX_BC_ROWS;
-constexpr int CPT = (TAMAX * TB + 511) / 512;  // band cells per thread in the epilogue
-constexpr int BC_THREADS = 512;
-constexpr int BC_WAVES = BC_THREADS / 64;
-static_assert(BC_WAVES == 8, "unit -> (wave, slot) is decoded with shifts");
-constexpr int UPW_FULL = 6;                   // (type, x-tile) units per wave per pass
-constexpr int TPP_FULL = BC_WAVES * UPW_FULL / 3;  // types per pass (16)
-constexpr int DUMP_UNIT = 16 * ROWS;          // floats of one unit's 16 x 48 accumulator block
-
-struct BandArgs {
-    const void* v0;  // [k0][n][d]
-    const void* v1;
-    int n, m, d;
-    const float* inv0;  // [k][n] or null
-    const float* inv1;
-    const float* nrm0;  // [k][n]
-    const float* nrm1;
-    const int* path;  // [A][2]
-    int A, W;
-    float* costs;  // [T][A][2W], or [A][T][2W] when atb != 0
-    int* boff;     // [A]
-    int* status;   // set to SVX_ERR_PATH when the path is not a unit-step lattice path
-    int atb;
-};
-
-// LDS map of a band workgroup: [header: path chunk, types, row pointers, per-row scalars][work area].
-// The work area holds the k-slab rows during the k loop and, afterwards, the accumulator dump and
-// the output block Fs.  SW = slab width in 128-byte units (1 or 2).
-struct BandLds {
-    size_t off_rowptr, off_scal, off_work, work_bytes, total;
-    int rs;  // slab row stride in bytes
-};
-__host__ __device__ inline BandLds band_lds(int kx, int ky, int sw, int ntypes_pass) {
-    BandLds L;
-    const int NR = (kx + ky) * ROWS;
-    size_t o = (2 * TAMAX + 2 * (SVX_MAX_TYPES + 2)) * sizeof(int);  // spx, spy, tx, ty
-    L.off_rowptr = (o + 15) & ~(size_t)15;
-    o = L.off_rowptr + (size_t)NR * sizeof(char*);
-    L.off_scal = (o + 15) & ~(size_t)15;
-    o = L.off_scal + 2 * (size_t)NR * sizeof(float);  // normaliser and inverse norm per staged row
-    L.off_work = (o + 15) & ~(size_t)15;
-    L.rs = sw * 128 + 16;
-    const size_t slab = (size_t)NR * L.rs;
-    const size_t fs = (size_t)ntypes_pass * TAMAX * TB * sizeof(float);
-    const size_t epi = fs + (size_t)BC_WAVES * DUMP_UNIT * sizeof(float);  // Fs + at least one dump round
-    L.work_bytes = slab > epi ? slab : epi;
-    L.total = L.off_work + L.work_bytes;
-    return L;
-}
-
-// `live` has bit i set when the thread's i-th piece belongs to a row the chunk really reads.  Dead rows
-// are neither loaded nor stored: an MFMA output element only depends on its own A row and B row, and
-// the epilogue never looks at elements of dead rows, so whatever the LDS holds there is harmless.
-template <typename E, int NPT, int SW>
-__device__ __forceinline__ void slab_load(uint4* pre, const char* const* rowptr, unsigned live, int k0, int d, int tid) {
-    using S = typename E::storage;
-    constexpr int PPR = 8 * SW;  // 16-byte pieces per row
-#pragma unroll
-    for (int i = 0; i < NPT; i++) {
-        const int q = tid + i * BC_THREADS;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if ((live >> i) & 1u) {
-            const int r = q / PPR, p = q % PPR;
-            const int kel = k0 + p * E::VEC;
-            if (kel < d) v = *reinterpret_cast<const uint4*>(rowptr[r] + (size_t)kel * sizeof(S));
-        }
-        pre[i] = v;
-    }
-}
-template <int NPT, int SW>
-__device__ __forceinline__ void slab_store(const uint4* pre, char* slab, unsigned live, int tid) {
-    constexpr int PPR = 8 * SW, RSB = SW * 128 + 16;
-#pragma unroll
-    for (int i = 0; i < NPT; i++) {
-        const int q = tid + i * BC_THREADS;
-        if ((live >> i) & 1u) *reinterpret_cast<uint4*>(slab + (q / PPR) * RSB + (q % PPR) * 16) = pre[i];
-    }
-}
-
-// NPT = 16-byte pieces a thread stages per k-slab: ceil((kx+ky)*48*8*SW / 512)
-template <typename E, int NPT, int SW>
-__device__ void band_block(const BandArgs& g, const SvxTypes& ty, int kx, int ky, int a0, int TAe, int chunk_b, char* smem) {
-    using S = typename E::storage;
-    using M = Mma<E>;
-    constexpr int RSB = SW * 128 + 16;
-    constexpr int KSB = M::KS * SW, NKB = M::NK * SW;
-    // 512-byte slabs are only used for single-layer levels (<= 2 types): one unit per wave keeps the
-    // accumulators at 12 registers so that several workgroups share a CU and hide the load latency
-    constexpr int UPW = (SW == 4) ? 1 : UPW_FULL;
-    constexpr int TPP = BC_WAVES * UPW / 3;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int B = 2 * g.W;
-    const int b0 = chunk_b * TB;
-    const int TBe = (B - b0) < TB ? (B - b0) : TB;
-    const int NR = (kx + ky) * ROWS;
-    const int npieces = NR * 8 * SW;
-    const BandLds L = band_lds(kx, ky, SW, ty.n < TPP ? ty.n : TPP);
-    int* spx = reinterpret_cast<int*>(smem);
-    int* spy = spx + TAMAX;
-    int* ltx = spy + TAMAX;                    // alignment type sizes (kernel-argument arrays cannot be indexed
-    int* lty = ltx + (SVX_MAX_TYPES + 2);     //  dynamically without a trip through scratch)
-    const char** rowptr = reinterpret_cast<const char**>(smem + L.off_rowptr);
-    float* snrm = reinterpret_cast<float*>(smem + L.off_scal);  // [NR] normaliser of each staged row
-    float* sinv = snrm + NR;                                     // [NR] inverse norm (1 when rows are unit)
-    char* slab = smem + L.off_work;
-
-    if (tid < TAe) {
-        spx[tid] = g.path[2 * (a0 + tid)];
-        spy[tid] = g.path[2 * (a0 + tid) + 1];
-    }
-    for (int t = tid; t < ty.n; t += BC_THREADS) {
-        ltx[t] = ty.x[t];
-        lty[t] = ty.y[t];
-    }
-    __syncthreads();
-    if (tid < TAe) {
-        bool ok = (spx[tid] + spy[tid] == a0 + tid);
-        if (tid > 0) ok = ok && spx[tid] >= spx[tid - 1] && spy[tid] >= spy[tid - 1];
-        if (!ok && g.status) *g.status = SVX_ERR_PATH;
-        if (chunk_b == 0) g.boff[a0 + tid] = spy[tid] - g.W;
-    }
-    const int xlo = spx[0], ylo = spy[0];
-    const int X0 = xlo + g.W - (b0 + TBe - 1);
-    const int Y0 = ylo - g.W + b0;
-    // rows the chunk's cells actually touch: (x_hi - x_lo) + TBe on the source side, same on the target
-    // side; the remaining staging rows stay zero and cost no global traffic
-    const int NXn = spx[TAe - 1] - xlo + TBe, NYn = spy[TAe - 1] - ylo + TBe;
-    for (int r = tid; r < NR; r += BC_THREADS) {
-        const int side = r >= kx * ROWS;
-        const int rr = side ? r - kx * ROWS : r;
-        const int layer = rr / ROWS, loc = rr % ROWS;
-        const int gi = (side ? Y0 : X0) + loc;
-        const int nn = side ? g.m : g.n;
-        const bool live = loc < (side ? NYn : NXn) && gi >= 0 && gi < nn;
-        const char* base = reinterpret_cast<const char*>(side ? g.v1 : g.v0);
-        rowptr[r] = live ? base + ((size_t)layer * nn + gi) * g.d * sizeof(S) : nullptr;
-        const float* nr = side ? g.nrm1 : g.nrm0;
-        const float* iv = side ? g.inv1 : g.inv0;
-        snrm[r] = live ? nr[(size_t)layer * nn + gi] : 0.f;
-        sinv[r] = (live && iv) ? iv[(size_t)layer * nn + gi] : 1.f;
-    }
-    __syncthreads();
-    const int loff = (lane & 15) * RSB + (int)(sizeof(S) == 4 ? 4 : 16) * (lane >> 4);
-    unsigned live = 0;
-#pragma unroll
-    for (int i = 0; i < NPT; i++) {
-        const int q = tid + i * BC_THREADS;
-        if (q < npieces && rowptr[q / (8 * SW)] != nullptr) live |= 1u << i;
-    }
-    // 16-row tiles that hold live rows: nxt x nyt of the 3 x 3 (4 of 9 for a diagonal path)
-    const int nxt = NXn <= 16 ? 1 : (NXn <= 32 ? 2 : 3);
-    const int nyt = NYn <= 16 ? 1 : (NYn <= 32 ? 2 : 3);
-
-    // this thread's output cells (CPT per thread: TAe * TBe <= TAMAX * TB)
-    const int ncells = TAe * TBe;
-    int c_ai[CPT], c_bi[CPT], c_xloc[CPT], c_yloc[CPT];
-    bool c_in[CPT];
-#pragma unroll
-    for (int cc = 0; cc < CPT; cc++) {
-        const int cell = tid + cc * BC_THREADS;
-        c_ai[cc] = cell / TBe;
-        c_bi[cc] = cell - c_ai[cc] * TBe;
-        c_xloc[cc] = 0;
-        c_yloc[cc] = 0;
-        c_in[cc] = false;
-        if (cell < ncells) {
-            const int yy = spy[c_ai[cc]] - g.W + b0 + c_bi[cc];
-            const int xx = (a0 + c_ai[cc]) - yy;
-            c_xloc[cc] = xx - X0;  // 0 <= xloc, yloc < ROWS for a unit-step path
-            c_yloc[cc] = yy - Y0;
-            c_in[cc] = xx >= 0 && xx < g.n && yy >= 0 && yy < g.m;
-            if (c_xloc[cc] < 0 || c_xloc[cc] >= ROWS || c_yloc[cc] < 0 || c_yloc[cc] >= ROWS) { c_xloc[cc] = 0; c_yloc[cc] = 0; c_in[cc] = false; }
-        }
-    }
-
-    for (int pass = 0; pass * TPP < ty.n; pass++) {
-        const int ntp = (ty.n - pass * TPP) < TPP ? (ty.n - pass * TPP) : TPP;
-        const int nunits = ntp * nxt;  // (type, live x tile)
-        // With at most 4 units (a single alignment type: the deeper pyramid levels) two waves share a unit
-        // and split its k-steps (even / odd); the epilogue adds the two partial dumps.
-        const bool ksplit = nunits <= 4;
-        const int khalf = ksplit ? (wave >> 2) : 0;
-        f32x4_t acc[UPW][3];
-        int aoff[UPW], boffs[UPW];  // LDS byte offsets of the unit's x tile rows / its type's y layer
-        int uid[UPW];
-#pragma unroll
-        for (int s = 0; s < UPW; s++) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) acc[s][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-            const int u = ksplit ? (s == 0 ? (wave & 3) : nunits) : wave + BC_WAVES * s;
-            uid[s] = u;
-            const int t = pass * TPP + (u < nunits ? u / nxt : 0);
-            const int xt = u % nxt;
-            aoff[s] = ((ltx[t] - 1) * ROWS + xt * 16) * RSB + loff;
-            boffs[s] = ((kx + lty[t] - 1) * ROWS) * RSB + loff;
-        }
-        auto mma_slab = [&]() {
-#pragma unroll
-            for (int s = 0; s < UPW; s++) {
-                if (uid[s] < nunits) {  // wave-uniform
-                    const char* ap = slab + aoff[s];
-                    const char* bp = slab + boffs[s];
-                    if (ksplit) {
-#pragma unroll
-                        for (int ks2 = 0; ks2 < NKB / 2; ks2++) {
-                            const int ko = (2 * ks2 + khalf) * M::KSTEP_BYTES;
-                            const typename M::frag fa = M::load(ap + ko);
-#pragma unroll
-                            for (int j = 0; j < 3; j++)
-                                if (j < nyt) M::mma(acc[s][j], fa, M::load(bp + j * 16 * RSB + ko));
-                        }
-                    } else {
-#pragma unroll
-                        for (int ks = 0; ks < NKB; ks++) {
-                            const typename M::frag fa = M::load(ap + ks * M::KSTEP_BYTES);
-#pragma unroll
-                            for (int j = 0; j < 3; j++)
-                                if (j < nyt) M::mma(acc[s][j], fa, M::load(bp + j * 16 * RSB + ks * M::KSTEP_BYTES));
-                        }
-                    }
-                }
-            }
-        };
-        if constexpr (SW == 1) {
-            // 128-byte slabs: two register sets, so every global load has two slab periods to land
-            // (slab k in LDS, slab k+1 in flight in one set, slab k+2 being issued into the other)
-            uint4 preA[NPT], preB[NPT];
-            slab_load<E, NPT, SW>(preA, rowptr, live, 0, g.d, tid);
-            __syncthreads();  // the previous pass is done with the work area
-            slab_store<NPT, SW>(preA, slab, live, tid);
-            if (KSB < g.d) slab_load<E, NPT, SW>(preA, rowptr, live, KSB, g.d, tid);
-            __syncthreads();
-            for (int k0 = 0; k0 < g.d; k0 += 2 * KSB) {
-                if (k0 + 2 * KSB < g.d) slab_load<E, NPT, SW>(preB, rowptr, live, k0 + 2 * KSB, g.d, tid);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_slab();
-                __syncthreads();  // every wave has read this slab
-                if (k0 + KSB < g.d) {
-                    slab_store<NPT, SW>(preA, slab, live, tid);
-                    __syncthreads();
-                    if (k0 + 3 * KSB < g.d) slab_load<E, NPT, SW>(preA, rowptr, live, k0 + 3 * KSB, g.d, tid);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mma_slab();
-                    __syncthreads();
-                    if (k0 + 2 * KSB < g.d) slab_store<NPT, SW>(preB, slab, live, tid);
-                    __syncthreads();
-                }
-            }
-        } else {
-            // wide slabs: the global loads of slab k+1 are issued before the MFMAs of slab k
-            uint4 pre[NPT];
-            slab_load<E, NPT, SW>(pre, rowptr, live, 0, g.d, tid);
-            __syncthreads();  // the previous pass is done with the work area
-            slab_store<NPT, SW>(pre, slab, live, tid);
-            __syncthreads();
-            for (int k0 = 0; k0 < g.d; k0 += KSB) {
-                const bool more = k0 + KSB < g.d;
-                if (more) slab_load<E, NPT, SW>(pre, rowptr, live, k0 + KSB, g.d, tid);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_slab();
-                __syncthreads();  // every wave has read this slab
-                if (more) slab_store<NPT, SW>(pre, slab, live, tid);
-                __syncthreads();
-            }
-        }
-        // epilogue.  Work area = Fs [ai][type][bi] followed by the accumulator dump [unit][16][48].
-        // Rounds of SR unit slots: dump -> every thread looks its cell up in each dumped unit whose x tile
-        // contains the cell's row -> cost formula -> Fs.  Finally Fs is written out coalesced.
-        float* Fs = reinterpret_cast<float*>(slab);
-        float* dump = Fs + (size_t)ntp * TAMAX * TB;
-        const int du = (int)((L.work_bytes - (size_t)ntp * TAMAX * TB * sizeof(float)) / (DUMP_UNIT * sizeof(float)));
-        const int SR = du / BC_WAVES >= UPW ? UPW : (du / BC_WAVES < 1 ? 1 : du / BC_WAVES);
-        const int nslots = (nunits + BC_WAVES - 1) / BC_WAVES;
-        for (int s0 = 0; s0 < nslots; s0 += SR) {
-#pragma unroll
-            for (int s = 0; s < UPW; s++) {
-                if (s >= s0 && s < s0 + SR && uid[s] < nunits) {
-                    float* dw = dump + ((s - s0) * BC_WAVES + wave) * DUMP_UNIT;
-#pragma unroll
-                    for (int yt = 0; yt < 3; yt++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) dw[((lane >> 4) * 4 + r) * ROWS + yt * 16 + (lane & 15)] = acc[s][yt][r];
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int cc = 0; cc < CPT; cc++) {
-                if (tid + cc * BC_THREADS >= ncells) continue;
-                const int xq = c_xloc[cc] >> 4;
-                const int ulo = s0 * BC_WAVES, uhi = (s0 + SR) * BC_WAVES < nunits ? (s0 + SR) * BC_WAVES : nunits;
-                // units of this round whose x tile holds my row: u = nxt*tl + xq
-                for (int tl = (ulo - xq + nxt - 1) / nxt; nxt * tl + xq < uhi; tl++) {
-                    const int u = nxt * tl + xq;
-                    const int t = pass * TPP + tl;
-                    const int p = ltx[t], q = lty[t];
-                    float c = __builtin_inff();
-                    if (c_in[cc]) {
-                        const int rx = (p - 1) * ROWS + c_xloc[cc], ry = (kx + q - 1) * ROWS + c_yloc[cc];
-                        float dsum = dump[(u - ulo) * DUMP_UNIT + (c_xloc[cc] & 15) * ROWS + c_yloc[cc]];
-                        if (ksplit) dsum += dump[(u - ulo + 4) * DUMP_UNIT + (c_xloc[cc] & 15) * ROWS + c_yloc[cc]];
-                        const float sumx = dsum * sinv[rx] * sinv[ry];
-                        c = cost_formula(sumx, p, q, snrm[rx], snrm[ry]);
-                    }
-                    Fs[((size_t)c_ai[cc] * ntp + tl) * TB + c_bi[cc]] = c;
-                }
-            }
-            __syncthreads();
-        }
-        // coalesced write-out of the [ai][type][bi] block
-        const int nout = TAe * ntp * TBe;
-        for (int idx = tid; idx < nout; idx += BC_THREADS) {
-            const int ai = idx / (ntp * TBe);
-            const int rem = idx - ai * (ntp * TBe);
-            const int tl = rem / TBe, bi = rem - tl * TBe;
-            const int t = pass * TPP + tl;
-            const size_t o = g.atb ? ((size_t)(a0 + ai) * ty.n + t) * B + (b0 + bi) : ((size_t)t * g.A + (a0 + ai)) * B + (b0 + bi);
-            g.costs[o] = Fs[((size_t)ai * ntp + tl) * TB + bi];
-        }
-    }
-}
-
-template <typename E, int NPT, int SW>
-__global__ __launch_bounds__(BC_THREADS) void k_band_costs(BandArgs g, SvxTypes ty, int kx, int ky, int nchunk_b) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int a0 = (blockIdx.x / nchunk_b) * TA;
-    band_block<E, NPT, SW>(g, ty, kx, ky, a0, (g.A - a0) < TA ? (g.A - a0) : TA, blockIdx.x % nchunk_b, smem);
-}
-
-// depth 0 uses the final types on the raw rows; deeper levels use (1,1) on normalised fp32 layer 0
-// depth 0 uses the final types on the raw rows; deeper levels use (1,1) on normalised fp32 layer 0
-// Workgroups are dealt round-robin over the 8 XCDs (id % 8).  Remap the linear id so that each XCD
-// owns one contiguous range of (pair, chunk) work items: neighbouring chunks share up to 2W rows per
-// side, and with this map they share them through the same L2 (speed only, never correctness).
-__device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned n) {
-    const unsigned q = n / 8, r = n % 8, xcd = id % 8, k = id / 8;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-
-// depth 0 uses the final types on the raw rows; deeper levels use (1,1) on normalised fp32 layer 0
-template <typename E, bool LV0, int NPT, int SW>
-__global__ __launch_bounds__(BC_THREADS) void k_band_costs_batch(const SvxPairDev* __restrict__ pairs, int depth, SvxTypes ty,
-                                                                 int kx, int ky, int W, int nchunk_b, int per_pair) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned wg = xcd_remap(blockIdx.x, gridDim.x);
-    const SvxPairDev& P = pairs[wg / per_pair];
-    const int item = wg % per_pair;
-    if (depth > P.L || (depth == P.L && P.L > 0)) return;  // refined levels only (or level 0 when L == 0)
-    const SvxLevel& Lv = P.lev[depth];
-    BandArgs g;
-    g.A = *Lv.path_len;
-    const int chunk_a = item / nchunk_b;
-    if (g.A <= 0 || chunk_a >= *Lv.nchunks) return;
-    const int a0 = Lv.cstart[chunk_a], TAe = Lv.cstart[chunk_a + 1] - a0;
-    g.n = Lv.n[0];
-    g.m = Lv.n[1];
-    g.d = P.d;
-    g.v0 = LV0 ? P.v[0] : (const void*)Lv.P[0];
-    g.v1 = LV0 ? P.v[1] : (const void*)Lv.P[1];
-    g.inv0 = LV0 ? Lv.inv[0] : nullptr;
-    g.inv1 = LV0 ? Lv.inv[1] : nullptr;
-    g.nrm0 = Lv.nrm[0];
-    g.nrm1 = Lv.nrm[1];
-    g.path = Lv.path;
-    g.W = W;
-    g.costs = Lv.costs;
-    g.boff = Lv.boff;
-    g.status = P.status;
-    g.atb = 1;
-    band_block<E, NPT, SW>(g, ty, kx, ky, a0, TAe, item % nchunk_b, smem);
-}
-
 inline int nch_f32(int d) {
     int c = (d + 255) / 256;
     return c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 8;
@@ -1070,137 +688,5 @@ int svxl_knob_scores(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, int max
 #undef M32
 #undef M16
     SVX_LAUNCH_CHECK(ctx, "k_knob_scores");
-    return SVX_OK;
-}
-
-static int types_layers(const SvxTypes& ty, int* kx, int* ky) {
-    int mx = 0, my = 0;
-    for (int t = 0; t < ty.n; t++) {
-        if (ty.x[t] > mx) mx = ty.x[t];
-        if (ty.y[t] > my) my = ty.y[t];
-    }
-    *kx = mx;
-    *ky = my;
-    return 0;
-}
-
-struct BandPlan {
-    int sw, npt;
-    size_t smem;
-};
-
-// Slab width and staging depth for a layer count: the widest k-slab the LDS budget allows (512 bytes for
-// single-layer levels, else 256, else 128): wider slabs mean fewer barrier rounds per workgroup.
-static int band_plan(svx_ctx* ctx, int kx, int ky, int ntypes, BandPlan* bp) {
-    const int NR = (kx + ky) * ROWS;
-    const char* sw_env = getenv("SVX_BAND_SW");  // tuning override: widest slab to consider
-    const int sw_max = sw_env ? atoi(sw_env) : 4;
-    for (int sw = 4; sw >= 1; sw >>= 1) {
-        if (sw > sw_max) continue;
-        const int tpp = sw == 4 ? BC_WAVES / 3 : TPP_FULL;
-        const int ntp = ntypes < tpp ? ntypes : tpp;
-        if (sw == 4 && ntypes > tpp) continue;
-        const BandLds L = band_lds(kx, ky, sw, ntp);
-        const int npt = (NR * 8 * sw + BC_THREADS - 1) / BC_THREADS;
-        if (sw == 4 && (NR > 2 * ROWS || L.total > 64 * 1024)) continue;  // 512-byte slabs: single-layer levels only
-        if (sw == 2 && (L.total > 128 * 1024 || npt > 12)) continue;
-        if (L.total > 160 * 1024 || npt > 14)
-            return svx_fail(ctx, SVX_ERR_ARG, "band costs: %d+%d overlap layers need %zu bytes of LDS / %d staging pieces (limits 160 KiB / 14)",
-                            kx, ky, L.total, npt);
-        bp->sw = sw;
-        bp->npt = npt < 1 ? 1 : npt;
-        bp->smem = L.total;
-        return SVX_OK;
-    }
-    return svx_fail(ctx, SVX_ERR_ARG, "band costs: no launch configuration");
-}
-
-#define BAND_DISPATCH(CALL)                      \
-    do {                                         \
-        if (bp.sw == 4) {                        \
-            CALL(6, 4);                          \
-        } else if (bp.sw == 2) {                 \
-            if (bp.npt <= 3) CALL(3, 2);         \
-            else if (bp.npt <= 6) CALL(6, 2);    \
-            else CALL(12, 2);                    \
-        } else {                                 \
-            if (bp.npt <= 2) CALL(2, 1);         \
-            else if (bp.npt <= 6) CALL(6, 1);    \
-            else if (bp.npt <= 8) CALL(8, 1);    \
-            else CALL(14, 1);                    \
-        }                                        \
-    } while (0)
-
-int svxl_band_costs(svx_ctx* ctx, const void* v0, int k0, int n, const void* v1, int k1, int m, int d, int dtype,
-                    const float* inv0, const float* inv1, const float* nrm0, const float* nrm1, const int* path, int A,
-                    const SvxTypes& types, int W, float* costs, int* boff, int* status) {
-    if (A <= 0) return SVX_OK;
-    int kx, ky;
-    types_layers(types, &kx, &ky);
-    if (kx > k0 || ky > k1) return svx_fail(ctx, SVX_ERR_OVERLAPS, "overlaps");
-    if (types.n == 0) kx = ky = 0;  // only b_offset is produced (costs has shape [0][A][B])
-    BandPlan bp;
-    int rc = band_plan(ctx, kx, ky, types.n, &bp);
-    if (rc) return rc;
-    const size_t smem = bp.smem;
-    const int B = 2 * W;
-    const int nca = (A + TA - 1) / TA, ncb = (B + TB - 1) / TB;
-    BandArgs g{v0, v1, n, m, d, inv0, inv1, nrm0, nrm1, path, A, W, costs, boff, status, 0};
-    dim3 grid((unsigned)(nca * ncb));
-#define CALL_E(E, NPT, SW)                                                                                          \
-    do {                                                                                                            \
-        if (smem > 64 * 1024)                                                                                       \
-            SVX_HIP(ctx, hipFuncSetAttribute((const void*)k_band_costs<E, NPT, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        hipLaunchKernelGGL((k_band_costs<E, NPT, SW>), grid, dim3(BC_THREADS), smem, ctx->stream, g, types, kx, ky, ncb); \
-    } while (0)
-#define CALL_F32(NPT, SW) CALL_E(ElemF32, NPT, SW)
-#define CALL_F16(NPT, SW) CALL_E(ElemF16, NPT, SW)
-#define CALL_BF16(NPT, SW) CALL_E(ElemBF16, NPT, SW)
-    if (dtype == SVX_F32) BAND_DISPATCH(CALL_F32);
-    else if (dtype == SVX_F16) BAND_DISPATCH(CALL_F16);
-    else BAND_DISPATCH(CALL_BF16);
-#undef CALL_F32
-#undef CALL_F16
-#undef CALL_BF16
-#undef CALL_E
-    SVX_LAUNCH_CHECK(ctx, "k_band_costs");
-    return SVX_OK;
-}
-
-int svxl_band_costs_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, int depth, int max_A, const SvxTypes& types,
-                          int W, int dtype, int d) {
-    (void)d;
-    if (n_pairs <= 0 || max_A <= 0) return SVX_OK;
-    int kx, ky;
-    types_layers(types, &kx, &ky);
-    if (types.n == 0) kx = ky = 0;
-    BandPlan bp;
-    int rc = band_plan(ctx, kx, ky, types.n, &bp);
-    if (rc) return rc;
-    const size_t smem = bp.smem;
-    const int B = 2 * W;
-    const int nca = (max_A + TA - 1) / TA, ncb = (B + TB - 1) / TB;
-    const int per_pair = nca * ncb;
-    dim3 grid((unsigned)per_pair * (unsigned)n_pairs);
-#define CALL_E(E, LV0, NPT, SW)                                                                                     \
-    do {                                                                                                            \
-        if (smem > 64 * 1024)                                                                                       \
-            SVX_HIP(ctx, hipFuncSetAttribute((const void*)k_band_costs_batch<E, LV0, NPT, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        hipLaunchKernelGGL((k_band_costs_batch<E, LV0, NPT, SW>), grid, dim3(BC_THREADS), smem, ctx->stream, pairs, depth, types, kx, ky, W, ncb, per_pair); \
-    } while (0)
-#define CALL_DEEP(NPT, SW) CALL_E(ElemF32, false, NPT, SW)
-#define CALL_F32(NPT, SW) CALL_E(ElemF32, true, NPT, SW)
-#define CALL_F16(NPT, SW) CALL_E(ElemF16, true, NPT, SW)
-#define CALL_BF16(NPT, SW) CALL_E(ElemBF16, true, NPT, SW)
-    if (depth > 0) BAND_DISPATCH(CALL_DEEP);
-    else if (dtype == SVX_F32) BAND_DISPATCH(CALL_F32);
-    else if (dtype == SVX_F16) BAND_DISPATCH(CALL_F16);
-    else BAND_DISPATCH(CALL_BF16);
-#undef CALL_DEEP
-#undef CALL_F32
-#undef CALL_F16
-#undef CALL_BF16
-#undef CALL_E
-    SVX_LAUNCH_CHECK(ctx, "k_band_costs_batch");
     return SVX_OK;
 }

@@ -1128,8 +1128,9 @@ __global__ __launch_bounds__(256) void k_search_path_batch(const SvxPairDev* __r
     }
 }
 
-// Band-cost chunks of the fused pipeline: as many path points as possible (<= SVX_BC_TAMAX) whose source and
-// target extents both stay within SVX_BC_ROWS - SVX_BC_TB rows, so that a chunk's cells never leave the rows its
+// Band-cost chunks of the fused pipeline: as many path points as possible (<= TAMAX = 2 LIM + 1) that advance at
+// most LIM rows on either side, LIM = the rows the level's band-cost kernel stages per side less the band cells of a
+// workgroup (svxl_band2_limits: 32 or 64 rows, min(2W, 16) cells), so that a chunk's cells never leave the rows its
 // workgroup stages.  The end of the chunk that starts at s is found for every s at once (the path is monotone:
 // binary search), then thread 0 hops from chunk start to chunk start.
 __global__ __launch_bounds__(256) void k_chunk_path(const SvxPairDev* __restrict__ pairs, int depth, int lds_ints, int LIM, int TAMAX) {

@@ -13,8 +13,9 @@ integer outputs (b_offset) and the pattern of infinite cells bit for bit.  Each 
 ("iid") and with common=1.4 ("aniso").  tests/test_op_ref_cpu.py guards the reference side of every case below on the
 CPU (it imports the tables of this file).
 
-Which case selects which instantiation (read off nch_f32 / band_plan; profiles/op_matrix_kernels.txt is the kernel
-trace of this file, checked against this table):
+Which case selects which instantiation (read off nch_f32 / choose_variant and make_plan of svx_band.hip, which
+tests/test_op_ref_cpu.py restates; profiles/op_matrix_kernels.txt is the kernel trace of this file, checked against
+this table):
 
     d = 8, 256            NCH 1 (one 16-byte piece; every lane of the only chunk full)
     d = 264, 512          NCH 2 (first lanes of the second chunk; both chunks full)
@@ -24,22 +25,25 @@ trace of this file, checked against this table):
     compute_norms "rows33000" (d = 8)    k_rownorms_plain's grid-stride loop (more than 8192 workgroups of 4 rows)
     score_path n = 70001 (d = 8, 264)    k_score_path's grid-stride loop (more than 16384 workgroups of 4 rows)
 
-    band set      types                              layers  k_band_costs<ElemF32, NPT, SW>
-    t1            [(1, 1)]                           1 + 1   6, 4
-    t3            alignment_types(3)                 2 + 2   6, 2
-    m21           [(1, 1), (2, 1)]                   2 + 1   6, 2
-    t4, t5        alignment_types(4), (5)            3 + 3, 4 + 4    12, 2
-    t6            alignment_types(6)                 5 + 5   8, 1
-    t7            alignment_types(7), 21 types       6 + 6   14, 1 (two type passes)
-    t10           alignment_types(10), 45 types      9 + 9   14, 1 (three passes; the layer limit)
-    rep           [(1, 1)] * 3                       1 + 1   3, 2 (more than two types on two layers needs a repeated
-                                                             type; the oracle, like dp_core.pyx, loops over the list
-                                                             and accepts it)
-    sw1_t1        [(1, 1)], SVX_BAND_SW=1            1 + 1   2, 1
-    sw1_t4        alignment_types(4), SVX_BAND_SW=1  3 + 3   6, 1
+    band set      types                      layers   k_band_costs2_op<ElemF32, ROWS, NSLOT, UPW, S>, passes
+    t1            [(1, 1)]                   1 + 1    64, 2, 1, 4     1
+    rep           [(1, 1)] * 3               1 + 1    32, 8, 5, 3     1  (more than one type on two layers needs a repeated
+                                                                         type; the oracle, like dp_core.pyx, loops over
+                                                                         the list and accepts it)
+    m21           [(1, 1), (2, 1)]           2 + 1    32, 8, 5, 3     1
+    t3, t4, t5    alignment_types(3 .. 5)    .. 4 + 4 32, 8, 5, 3     1  (t5: all 8 slots, all 10 types of a pass)
+    t6            alignment_types(6)         5 + 5    32, 12, 8, 3    1
+    t7            alignment_types(7), 21     6 + 6    32, 20, 8, 2    2  (broken by the 16 types of a pass)
+    t10           alignment_types(10), 45    9 + 9    32, 20, 8, 2    3  (type limit)
+    t11           alignment_types(11), 55    10 + 10  32, 20, 8, 2    4  (type limit; 20 layers in all)
+    diag12        [(i, i) for i in 1 .. 12]  12 + 12  32, 20, 8, 2    2  (broken by the 20 slots of a pass: 10 + 2 types)
     straight      alignment_types(4), 40 x 150 docs, a straight path: part of the band lies outside the lattice
-  every set at d = 264 (two 128-byte slabs and a 32-byte tail slab at SW 1); t1, t4 and t7 also at d = 8, 1024, 2048;
-  W = 3, 9, 40 (B = 6, 18, 80: below one 16-cell band chunk, just above one, five chunks).
+    len135, len136     alignment_types(4) on 70 x 64, 70 x 65: with t4 (70 x 66, 137 points) the path is one short of,
+                       equal to and one over 8 chunks of lim + 1 = 17 points (32 rows, W = 9 and 40)
+    len146 .. len148   [(1, 1)] on 80 x 65 .. 67: the same around 3 chunks of 49 points (64 rows, W = 9 and 40)
+  every set at d = 264 (sixteen 64-byte k-slabs and a 32-byte tail); t1, t4 and t7 also at d = 8, 1024, 2048;
+  W = 3, 9, 40 (B = 6, 18, 80: below one 16-cell band chunk, just above one, five chunks).  The entry's [T][A][B] layout
+  always leaves through the kernel's cell-by-cell write-out (the 16-byte one is the pipeline layout's).
     dense_dp s0 = 2729 / 2730            ring of 3 (s0 + 1) doubles below / above 64 KiB (hipFuncSetAttribute branch)
     dense_dp s0 = 6399 / 6400            the largest ring / refused
 
@@ -80,19 +84,25 @@ SCORE_N = (1, 3, 4, 5, 4099)
 SCORE_BIG, SCORE_BIG_WIDTHS = 70001, (8, 264)            # past 16384 workgroups of 4 rows
 SHRUNK_ROWS = 300                                        # what the CPU guard puts in place of the two largest counts
 BAND_W = (3, 9, 40)
-BAND_SETS = {  # name: (types, SVX_BAND_SW or None, (n, m) or None for the 70 x 66 pair, (NPT, SW))
-    "t1": ([(1, 1)], None, None, (6, 4)),
-    "t3": (alignment_types(3), None, None, (6, 2)),
-    "m21": ([(1, 1), (2, 1)], None, None, (6, 2)),
-    "t4": (alignment_types(4), None, None, (12, 2)),
-    "t5": (alignment_types(5), None, None, (12, 2)),
-    "t6": (alignment_types(6), None, None, (8, 1)),
-    "t7": (alignment_types(7), None, None, (14, 1)),
-    "t10": (alignment_types(10), None, None, (14, 1)),
-    "rep": ([(1, 1)] * 3, None, None, (3, 2)),
-    "sw1_t1": ([(1, 1)], "1", None, (2, 1)),
-    "sw1_t4": (alignment_types(4), "1", None, (6, 1)),
-    "straight": (alignment_types(4), None, (40, 150), (12, 2)),
+R64, R32_8, R32_12, R32_20 = (64, 2, 1, 4), (32, 8, 5, 3), (32, 12, 8, 3), (32, 20, 8, 2)
+BAND_SETS = {  # name: (types, (n, m) with a straight path or None for the 70 x 66 pair, (ROWS, NSLOT, UPW, S), passes)
+    "t1": ([(1, 1)], None, R64, 1),
+    "rep": ([(1, 1)] * 3, None, R32_8, 1),
+    "m21": ([(1, 1), (2, 1)], None, R32_8, 1),
+    "t3": (alignment_types(3), None, R32_8, 1),
+    "t4": (alignment_types(4), None, R32_8, 1),
+    "t5": (alignment_types(5), None, R32_8, 1),
+    "t6": (alignment_types(6), None, R32_12, 1),
+    "t7": (alignment_types(7), None, R32_20, 2),
+    "t10": (alignment_types(10), None, R32_20, 3),
+    "t11": (alignment_types(11), None, R32_20, 4),
+    "diag12": ([(i, i) for i in range(1, 13)], None, R32_20, 2),
+    "straight": (alignment_types(4), (40, 150), R32_8, 1),
+    "len135": (alignment_types(4), (70, 64), R32_8, 1),
+    "len136": (alignment_types(4), (70, 65), R32_8, 1),
+    "len146": ([(1, 1)], (80, 65), R64, 1),
+    "len147": ([(1, 1)], (80, 66), R64, 1),
+    "len148": ([(1, 1)], (80, 67), R64, 1),
 }
 BAND_KEYS = [(s, 264) for s in BAND_SETS] + [(s, d) for d in (8, 1024, 2048) for s in ("t1", "t4", "t7")]
 DP_SHAPES = ((2729, 5), (2730, 5), (6399, 3), (5, 7000))
@@ -282,7 +292,7 @@ def straight_path(n, m):
 def cases_band(key, kind, shrink=False):
     orc = _oracle()
     name, d = key
-    types, sw, size, _ = BAND_SETS[name]
+    types, size = BAND_SETS[name][:2]
     n, m = size or (70, 66)
     K = max(max(x, y) for x, y in types)
     v0, v1 = _pair(n, m, K, d, _seed("band", name, d), kind)
@@ -292,9 +302,9 @@ def cases_band(key, kind, shrink=False):
     else:   # the search path of the oracle's dense alignment, as test_gpu_ops.test_sparse_ops_other_bands_vs_oracle builds it
         al = orc.dense_traceback(orc.dense_dp(orc.make_dense_costs(v0, v1, n0, n1), 0.4)[1])
         path = orc.search_path(al, False, n, m)
-    assert len(path) == n + m + 1 and len(path) % 32 != 0
+    assert len(path) == n + m + 1
     for W in BAND_W:
-        yield "W%d" % W, dict(v0=v0, v1=v1, n0=n0, n1=n1, path=path, types=types, W=W, sw=sw)
+        yield "W%d" % W, dict(v0=v0, v1=v1, n0=n0, n1=n1, path=path, types=types, W=W)
 
 
 def ref_band(a):
@@ -342,15 +352,9 @@ def judge(label, got, orc, f64):
     return None, rec
 
 
-def run_unit(op, key, kind, env, records=None):
-    """Every case of one (op, key, data kind) on the GPU.  env: pytest's monkeypatch (setenv / delenv).
-    -> list of failure texts"""
+def run_unit(op, key, kind, records=None):
+    """Every case of one (op, key, data kind) on the GPU.  -> list of failure texts"""
     cases, ref, gpu = OPS[op]
-    sw = BAND_SETS[key[0]][1] if op == "make_sparse_costs" else None
-    if sw is None:
-        env.delenv("SVX_BAND_SW", raising=False)
-    else:
-        env.setenv("SVX_BAND_SW", sw)    # read by band_plan on every call
     fails = []
     for name, a in cases(key, kind):
         label = "%s %s %s %s" % (op, key_name(key), name, kind)
@@ -371,8 +375,8 @@ def run_unit(op, key, kind, env, records=None):
 # ------------------------------------------------------------------------------------------------ the tests
 @pytest.mark.gpu
 @pytest.mark.parametrize("op,key,kind", UNITS, ids=["%s-%s-%s" % (o, key_name(k), kd) for o, k, kd in UNITS])
-def test_op_matrix(monkeypatch, op, key, kind):
-    fails = run_unit(op, key, kind, monkeypatch)
+def test_op_matrix(op, key, kind):
+    fails = run_unit(op, key, kind)
     assert not fails, "\n".join(fails)
 
 
@@ -394,21 +398,43 @@ def test_downsample_short_inputs():
     assert ctx.lib.svx_scratch_bytes(ctx.h) == before
 
 
+DIAG_REFUSED, DIAG_ACCEPTED = 81, 80   # [(i, i) for i in 1 .. k]: two new slots per type, 10 types per 20-slot pass
+
+
+def diag_types(k):
+    return [(i, i) for i in range(1, k + 1)]
+
+
 @pytest.mark.gpu
-def test_band_layer_limit_is_refused():
-    """alignment_types(11) needs 10 + 10 overlap layers: 15 staging pieces per thread, one more than the widest
-    instantiation; a following call on the same context works."""
+def test_band_pass_limit_is_refused():
+    """The per-op entry takes what the fused path takes: up to eight passes of the 20-slot shape.  81 types on 81 layers
+    per side need nine and are refused before anything is launched; the 80-type list needs eight, is accepted and is
+    judged by the rule of this file -- on the same context, right after the refusal."""
     from svx import _lib
     from svx.vecalign import dp_core
-    types = alignment_types(11)
-    v0, v1 = _pair(20, 22, 10, 8, 5, "iid")
+    v0, v1 = _pair(20, 22, DIAG_REFUSED, 8, 5, "iid")
     n0, n1 = _norms(v0, v1, 6)
     path = straight_path(20, 22)
-    with pytest.raises(_lib.SvxError, match=r"band costs: 10\+10 overlap layers need \d+ bytes of LDS / 15 staging pieces \(limits 160 KiB / 14\)"):
-        dp_core.make_sparse_costs(v0, v1, n0, n1, path, types, 3)
-    fo, bo = _oracle().make_sparse_costs(v0, v1, n0, n1, path, alignment_types(10), 3)
-    fg, bg = dp_core.make_sparse_costs(v0, v1, n0, n1, path, alignment_types(10), 3)
-    assert np.array_equal(bo, bg) and np.array_equal(np.isinf(fo), np.isinf(fg))
+    with pytest.raises(_lib.SvxError, match=r"band costs: no kernel shape for 81 alignment types"):
+        dp_core.make_sparse_costs(v0, v1, n0, n1, path, diag_types(DIAG_REFUSED), 3)
+    a = dict(v0=v0, v1=v1, n0=n0, n1=n1, path=path, types=diag_types(DIAG_ACCEPTED), W=3)
+    o, t = ref_band(a)
+    text, _ = judge("make_sparse_costs diag80", gpu_band(a, o), o, t)
+    assert text is None, text
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W", BAND_W)
+def test_band_empty_type_list(W):
+    """T = 0: the [0][A][B] cost array has no address; the kernel still validates the path and writes b_offset."""
+    from svx.vecalign import dp_core
+    v0, v1 = _pair(70, 66, 1, 8, 7, "iid")
+    n0, n1 = _norms(v0, v1, 8)
+    path = straight_path(70, 66)
+    fo, bo = _oracle().make_sparse_costs(v0, v1, n0, n1, path, [], W)
+    fg, bg = dp_core.make_sparse_costs(v0, v1, n0, n1, path, [], W)
+    assert fg.shape == fo.shape == (0, len(path), 2 * W) and fg.dtype == np.float32
+    assert bg.dtype == np.int32 and np.array_equal(bg, bo) and np.array_equal(bo, np.array(path)[:, 1] - W)
 
 
 @pytest.mark.gpu
@@ -494,14 +520,6 @@ def test_bad_dimension_is_refused_by_every_op():
 
 
 # ------------------------------------------------------------------------------------------------ dump mode
-class _Env:
-    def setenv(self, k, v):
-        os.environ[k] = v
-
-    def delenv(self, k, raising=True):
-        os.environ.pop(k, None)
-
-
 def main():
     import argparse
     ap = argparse.ArgumentParser()
@@ -511,7 +529,7 @@ def main():
     with open(a.dump, "w") as f:
         for op, key, kind in UNITS:
             records = []
-            fails = run_unit(op, key, kind, _Env(), records)
+            fails = run_unit(op, key, kind, records)
             for r in records:
                 f.write(json.dumps(dict(r, E_gpu=float("%.3e" % r['E_gpu']), E_orc=float("%.3e" % r['E_orc']), bound=float("%.3e" % r['bound'])),
                                    separators=(",", ":")) + "\n")
@@ -523,7 +541,6 @@ def main():
             print("%s %s %s: %d records, %d failures" % (op, key_name(key), kind, len(records), len(fails)), flush=True)
             for t in fails:
                 print("  " + t, flush=True)
-    _Env().delenv("SVX_BAND_SW")
     for op, (ratio, where) in worst.items():
         print("%s: worst E_gpu / bound %.3f (%s)" % (op, ratio, where))
     print("op matrix: %d units, %d failures" % (len(UNITS), bad))

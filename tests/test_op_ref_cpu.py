@@ -51,38 +51,111 @@ def test_case_tables_cover_what_the_matrix_promises():
     assert m.NORMS_BIG[1] * m.NORMS_BIG[2] == 33000 and m.NORMS_BIG[1] * m.NORMS_BIG[2] > 4 * 8192
     assert m.SCORE_BIG > 4 * 16384
     assert {(s, d) for s, d in m.BAND_KEYS if d == 264} == {(s, 264) for s in m.BAND_SETS}
-    assert {m.BAND_SETS[s][3] for s, _ in m.BAND_KEYS} == {(6, 4), (6, 2), (12, 2), (8, 1), (14, 1), (3, 2), (2, 1), (6, 1)}
+    assert {m.BAND_SETS[s][2] for s, _ in m.BAND_KEYS} == {m.R64, m.R32_8, m.R32_12, m.R32_20}
+    assert len(m.alignment_types(11)) == 55
     assert len(m.alignment_types(10)) == 45 and len(m.alignment_types(7)) == 21
     for s0, _ in m.DP_SHAPES[:2]:
         assert (3 * (s0 + 1) * 8 > 64 * 1024) == (s0 == 2730)
     assert 3 * 6400 * 8 == 150 * 1024
 
 
-def band_plan(types, sw_max=4):
-    """svx_costs.hip band_plan / BAND_DISPATCH restated for what decides the instantiation of these sets: staging pieces
-    per thread, the slab widths' layer / type limits (the LDS limits bind later than those for every set here)."""
-    kx, ky, T = max(x for x, _ in types), max(y for _, y in types), len(types)
-    for sw in (4, 2, 1):
-        if sw > sw_max:
-            continue
-        npt = -(-(kx + ky) * 48 * 8 * sw // 512)
-        if sw == 4 and (T > 2 or kx + ky > 2):
-            continue
-        if sw == 2 and npt > 12:
-            continue
-        if npt > 14:
+SHAPES = (m.R64, m.R32_8, m.R32_12, m.R32_20)   # choose_variant's options, in its order
+MAXPASS, WAVES = 8, 4                            # B2_MAXPASS, B2_WAVES
+
+
+def make_plan(types, tpp, nslot_max):
+    """svx_band.hip make_plan: consecutive types are packed into a pass while they fit its type and slot limits.
+    -> [(types in the pass, slots in use, what ended it: 'types' / 'slots' / 'end')] or None past MAXPASS passes."""
+    passes, t = [], 0
+    while t < len(types):
+        if len(passes) >= MAXPASS:
             return None
-        if sw == 4:
-            return 6, 4
-        if sw == 2:
-            return (3 if npt <= 3 else 6 if npt <= 6 else 12), 2
-        return (2 if npt <= 2 else 6 if npt <= 6 else 8 if npt <= 8 else 14), 1
+        xs, ys, nt, why = set(), set(), 0, 'end'
+        while t < len(types):
+            if nt >= tpp:
+                why = 'types'
+                break
+            x, y = types[t]
+            if len(xs | {x}) + len(ys | {y}) > nslot_max:
+                why = 'slots'
+                break
+            xs.add(x)
+            ys.add(y)
+            nt += 1
+            t += 1
+        if nt == 0:
+            return None
+        passes.append((nt, len(xs) + len(ys), why))
+    return passes
 
 
-def test_band_sets_select_the_instantiations_the_table_names():
-    for name, (types, sw, _, inst) in m.BAND_SETS.items():
-        assert band_plan(types, int(sw) if sw else 4) == inst, name
-    assert band_plan(m.alignment_types(11)) is None
+def choose_variant(types):
+    """svx_band.hip choose_variant -> ((ROWS, NSLOT, UPW, S), passes of make_plan) or None: the first shape that takes the
+    set in one pass, else whatever plan the last shape has."""
+    kx, ky = max([0] + [x for x, _ in types]), max([0] + [y for _, y in types])
+    for i, shape in enumerate(SHAPES):
+        rows, nslot, upw, _ = shape
+        tpp = WAVES * upw // (rows // 16)
+        if i < len(SHAPES) - 1 and (kx + ky > nslot or len(types) > tpp):
+            continue
+        plan = make_plan(types, tpp, nslot)
+        if plan is not None:
+            return shape, plan
+    return None
+
+
+def test_band_sets_select_the_shapes_the_table_names():
+    seen = set()
+    for name, (types, _, shape, npass) in m.BAND_SETS.items():
+        got = choose_variant(types)
+        assert got is not None and got[0] == shape and len(got[1]) == npass, (name, got)
+        seen.add(shape)
+    assert seen == set(SHAPES)
+    ends = {name: [why for _, _, why in choose_variant(m.BAND_SETS[name][0])[1]] for name in ("t7", "t10", "t11", "diag12")}
+    assert ends["t7"] == ['types', 'end'] and ends["t10"] == ['types', 'types', 'end'] and ends["t11"] == ['types'] * 3 + ['end']
+    assert ends["diag12"] == ['slots', 'end']
+    assert choose_variant([]) == (m.R64, [])       # T = 0: the first shape, no pass
+
+
+def test_band_path_lengths_sit_on_the_chunk_edges():
+    """Fixed chunks of lim + 1 = ROWS - min(2 W, 16) + 1 path points: the 32-row and the 64-row shape each see a path one
+    short of, equal to and one over a whole number of chunks (at W = 9 and 40, where a workgroup has 16 band cells)."""
+    for names, rows in ((("len135", "len136", "t4"), 32), (("len146", "len147", "len148"), 64)):
+        rest = []
+        for name in names:
+            types, size, shape, _ = m.BAND_SETS[name]
+            n, mm = size or (70, 66)
+            assert shape[0] == rows
+            rest.append((n + mm + 1) % (rows - 16 + 1))
+        assert rest == [rows - 16, 0, 1], (names, rest)
+
+
+def test_pass_limit_edge():
+    assert choose_variant(m.diag_types(m.DIAG_REFUSED)) is None
+    shape, plan = choose_variant(m.diag_types(m.DIAG_ACCEPTED))
+    assert shape == m.R32_20 and [p[:2] for p in plan] == [(10, 20)] * 8
+
+
+def test_every_set_of_the_retired_kernel_has_a_plan():
+    """What the first band-cost kernel took -- at most 18 overlap layers in all, at most 128 types -- is always planned:
+    no pass over <= 18 layers can run out of the 20 slots, so passes end at 16 types only and ceil(T / 16) <= 8."""
+    rs = np.random.RandomState(18)
+    sets = []
+    for kx in range(1, 18):
+        ky = 18 - kx
+        grid = [(x, y) for x in range(1, kx + 1) for y in range(1, ky + 1)]
+        worst = (grid * (128 // len(grid) + 1))[:128]           # every layer of both sides, the most types
+        sets += [worst, worst[::-1], [(kx, ky)] * 128]
+        for _ in range(20):
+            n = int(rs.randint(1, 129))
+            sets.append([(int(rs.randint(1, kx + 1)), int(rs.randint(1, ky + 1))) for _ in range(n)])
+    for types in sets:
+        got = choose_variant(types)
+        assert got is not None, types
+        plan = got[1]
+        assert sum(nt for nt, _, _ in plan) == len(types) and len(plan) <= MAXPASS
+        if got[0] == m.R32_20:
+            assert all(why != 'slots' for _, _, why in plan) and len(plan) == -(-len(types) // 16)
 
 
 def _drop_last_piece(a, keys):
