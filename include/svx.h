@@ -562,6 +562,64 @@ typedef struct svx_widen_params { int32_t guard, max_width_over2, max_rounds, re
 int svx_align_widen(svx_ctx *ctx, const svx_align_params *params, const svx_pair *pairs, const svx_prior *priors /* nullable */,
                     int n_pairs, const svx_widen_params *wp, int32_t *report /* HOST [n_pairs][4] */);
 
+/* ---- given alignments at the aligner's prices: search error or model error (csrc/svx_given.hip) ------------------
+ * svx_band_contact reports a symptom.  The test itself (search-error analysis) prices a path the caller believes in --
+ * gold, the timestamps' path, an earlier run, another tool's output -- with the normalisers and the deletion penalty the
+ * DP used, and compares its total with the total of the path the DP returned: a given path that is cheaper was missed by
+ * the search; one that is dearer is not what the model prefers, and no band width will find it.
+ *
+ * svx_score_alignments covers the pairs of the LAST svx_align_batch / svx_align_around call on the context, exactly as
+ * svx_band_contact does: both halves of a pipelined call, in the pair order of svx_debug_level; n_pairs must equal that
+ * call's pair count.  It calls svx_flush first and is asynchronous on the context's stream, with no host synchronisation.
+ * It reads level 0 of that call only: the caller's vectors, their dtype and d, k0 and k1, the level's n0 / n1, the inverse
+ * row norms 1/(||row|| + 1e-5) of the level-0 pass (the call's arena holds them until the next call: they are read, not
+ * formed again), the deletion penalty, new_b_offset, the search path's length, the band B = 2 * width_over2 and the call's
+ * type set.
+ * given (HOST [n_pairs]): rows / info as svx_pair.align / info and svx_prior.rows / info, 16-byte aligned, read only; they
+ * may be the pair's own align / info output, which is how a caller gets the total of the found path.  rows == NULL skips
+ * the pair: nothing of it is written.
+ *
+ * Row r < info[0], with p = x_len and q = y_len, n and m the sizes of the pair:
+ *   DELETION  exactly one of p, q is 1 and the other is 0, 0 <= x_start, x_start + p <= n, 0 <= y_start, y_start + q <= m.
+ *             Cost: the penalty.  scores[r] = 0.0 (process_scores, dp_utils.py:94-96).
+ *   PRICED    1 <= p <= k0, 1 <= q <= k1, in range as above.  With xe = x_start + p - 1, ye = y_start + q - 1:
+ *               dot = <V0[p-1][xe], V1[q-1][ye]> in fp32 x inv0[p-1][xe] x inv1[q-1][ye]
+ *               c   = fp32( 2 p q (1 - dot) / (1e-6 + (double) n0[p-1][xe] + (double) n1[q-1][ye]) )
+ *             -- the expression of the level-0 band-cost kernel.  scores[r] = max(c, 0) / (p q) as a double.
+ *             The row is OFF_TYPE as well when (p, q) is not in the call's type set.
+ *   WIDE      p, q >= 1 and in range, but p > k0 or q > k1: there is no candidate row.  scores[r] = NaN.
+ *   INVALID   anything else: a negative field, out of range, p = q = 0, a deletion of more than one segment.
+ *             scores[r] = NaN.
+ * A WIDE or INVALID row is never used to form an address: it may hold anything.
+ *   Nodes: node 0 is (0, 0), node i the end (x_start + p, y_start + q) of row i - 1.  Node (x, y) is OUTSIDE iff it is no
+ *   lattice node (0 <= x <= n, 0 <= y <= m), or a = x + y has no diagonal (a >= path_len + 2), or b = y - new_b_offset[a]
+ *   is not in [0, B).  The cost cell of a transition into a node has the node's b, so a path with no OUTSIDE node and no
+ *   OFF_TYPE, WIDE or INVALID row is one the DP could have returned.
+ *   COMPLETE: row 0 starts at (0, 0), every row starts where its predecessor ended, the last row ends at (n, m), and no
+ *   row is INVALID (a path without rows is not complete).
+ * report (device [8] int32, 16-byte aligned) = (rows, priced, deletions, wide, invalid, off_type, outside nodes, complete).
+ * total  (device [2] double): total[0] = sum of (double) c over the PRICED rows + penalty x deletions, total[1] = the
+ *   penalty.  The sum is formed in float64 in a fixed order -- row order inside a chunk of 256 rows, chunk order inside the
+ *   pair, the deletions' product last -- so it is the same from run to run.
+ * scores (device [cap] double, nullable): rows < info[0] as above, nothing past them.
+ * A pair with info[1] != 0, with info[0] outside [0, cap], or that failed in the aligner's call gets report = (-1 x 8) and
+ * total = (NaN, NaN); its scores are untouched.
+ * A null `given`, a negative n_pairs, a count that differs from the last call's, no earlier successful call, a null info /
+ * total / report beside non-null rows, a negative cap, or rows / report that are not 16-byte aligned return SVX_ERR_ARG
+ * with text and queue nothing.
+ * Two launches: one workgroup per chunk of 256 rows (a chunk never spans two pairs; per priced row two candidate rows are
+ * read, nothing else of that size), then one workgroup per pair.  Scratch (descriptors, the chunk table, per-chunk
+ * partial sums) is the context's post-processing scratch (svx_scratch_bytes). */
+typedef struct svx_given {
+    const int32_t *rows;   /* device [cap][4]: (x_start, x_len, y_start, y_len) */
+    const int32_t *info;   /* device [2]: info[0] = row count, info[1] != 0 -> the pair gets the -1 report */
+    int32_t cap, pad;
+    double *scores;        /* device [cap], nullable */
+    double *total;         /* device [2] */
+    int32_t *report;       /* device [8], 16-byte aligned */
+} svx_given;
+int svx_score_alignments(svx_ctx *ctx, const svx_given *given /* HOST [n_pairs] */, int n_pairs);
+
 /* Per-level intermediates of the LAST svx_align_batch call on this context -- the entries of the `stack` the reference
  * returns (dp_utils.py:412-537) -- as device pointers into the context's scratch arena (valid until the next call;
  * the scalar fields are read back, which synchronises the stream).  Pointers are NULL for what a level does not have

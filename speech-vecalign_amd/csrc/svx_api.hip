@@ -623,6 +623,18 @@ bool svxl_last_batch(svx_ctx* ctx, const SvxPairDev** host, int* n_pairs, int* b
     return true;
 }
 
+// What svxl_last_batch does not hand out: the call's storage type, its embedding dimension and its level-0 type set (both
+// halves of a pipelined call were planned with the same parameters).
+bool svxl_last_batch_types(svx_ctx* ctx, int* dtype, int* d, const SvxTypes** types) {
+    svx_ctx_ext* cx = X(ctx);
+    if (!cx->last_ok) return false;
+    const BatchParams& bp = cx->half[0].bp;
+    *dtype = bp.dtype;
+    *d = bp.d;
+    *types = &bp.tfinal;
+    return true;
+}
+
 // ------------------------------------------------------------------------------ plan of one half
 // Level sizes, scratch layout (inside the half's own arena) and launch extents of pairs[0 .. n).
 static int plan_half(svx_ctx* ctx, HalfState& H, const BatchParams& bp, const svx_align_params* prm, const svx_pair* pairs,

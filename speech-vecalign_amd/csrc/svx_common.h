@@ -338,3 +338,5 @@ int svxl_del_penalty_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int m
 int svxl_prior_ingest_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs);
 // band contact (svx_contact.hip reads the descriptors of the last batch: svx_api.hip)
 bool svxl_last_batch(svx_ctx*, const SvxPairDev** host, int* n_pairs, int* band);
+// storage type, embedding dimension and level-0 type set of that same call (svx_given.hip); false when there is none
+bool svxl_last_batch_types(svx_ctx*, int* dtype, int* d, const SvxTypes** types);

@@ -81,6 +81,13 @@ class WidenParams(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class Given(ctypes.Structure):
+    """svx_given: device rows [cap][4] and info [2] of a given alignment, and where its scores [cap], total [2] and
+    report [8] go (svx_score_alignments)."""
+    _fields_ = [("rows", c_vp), ("info", c_vp), ("cap", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("scores", c_vp), ("total", c_vp), ("report", c_vp)]
+
+
 class ConcatParams(ctypes.Structure):
     """svx_concat_params (include/svx.h)."""
     _fields_ = [
@@ -145,6 +152,7 @@ _SIGS = {
     "svx_band_contact": (c_int, [c_vp, c_int, c_int, c_vp]),
     "svx_align_widen": (c_int, [c_vp, ctypes.POINTER(AlignParams), ctypes.POINTER(Pair), ctypes.POINTER(Prior), c_int,
                                 ctypes.POINTER(WidenParams), c_vp]),
+    "svx_score_alignments": (c_int, [c_vp, ctypes.POINTER(Given), c_int]),
     "svx_alignment_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), c_int, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "svx_concat_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), ctypes.POINTER(Frames), c_int, ctypes.POINTER(ConcatParams), c_i64,
                                 c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),

@@ -30,6 +30,12 @@ it; that is host work on the results already fetched (filters.post_chain).
 (svx_band_contact): the sign that the band may have cut the best alignment off.  --widen searches such pairs again around
 their own result in twice the band until the path clears the edge (svx_align_widen; --widen_rounds, --widen_max_band,
 --widen_guard).  It removes search errors, not model errors, so it is opt-in; without these flags nothing changes.
+
+--rescore_dir DIR --rescore_tsv PATH answer the question the contact report leaves open: for every pair that has an
+alignment file DIR/{src}-{tgt}/{s}-{t}.txt (gold, an earlier run, another tool's output) that path is priced with the
+normalisers and the deletion penalty this run used (svx_score_alignments) and compared with the total of the path the DP
+returned: `search` when the given path is cheaper (the search missed it), `model` when it is dearer (no band will find it),
+`unpriced` when a row of it has no price.  The alignment files do not change.
 """
 import argparse
 import dataclasses
@@ -102,6 +108,14 @@ def parse_args(argv=None):
                    help="--widen: cells per diagonal at the most (default: the band in use times 2 ** widen_rounds)")
     p.add_argument("--widen_guard", type=int, default=0,
                    help="--widen / --contact_tsv: a node touches when it is at most this many cells from the edge")
+    p.add_argument("--rescore_dir", type=str, default=None,
+                   help="alignment files {rescore_dir}/{src}-{tgt}/{s}-{t}.txt (either line format of this job's outputs) to price with "
+                        "this run's costs (svx_score_alignments); a pair without one gives no line.  Needs --rescore_tsv")
+    p.add_argument("--rescore_tsv", type=str, default=None,
+                   help="--rescore_dir: write one line per pair, 'src tgt verdict found_total given_total del_penalty rows priced deletions "
+                        "wide invalid off_type outside complete' (tab-separated): verdict search = the given path is cheaper than the "
+                        "returned one, model = it is dearer, unpriced = it has rows without a price or is no complete path, invalid = "
+                        "the file is no monotone alignment (the numbers are then empty)")
     p.add_argument("--batch_size", type=int, default=32, help="document pairs per device pass")
     p.add_argument("--io_threads", type=int, default=None, help="host threads that parse / read ahead of the GPU (default: the CPU count, at most 32)")
     p.add_argument("--seed", type=int, default=None, help="derive one sampling stream per pair from (seed, pair index)")
@@ -143,6 +157,13 @@ def parse_args(argv=None):
         p.error("--widen_rounds and --widen_guard must be >= 0")
     if args.widen_max_band is not None and args.widen_max_band < 6:
         p.error("--widen_max_band must be at least 6")
+    if (args.rescore_dir is None) != (args.rescore_tsv is None):
+        p.error("--rescore_dir and --rescore_tsv go together")
+    if args.rescore_dir is not None and args.widen:
+        p.error("--rescore_dir cannot be combined with --widen: after band doubling the last device call holds only the pairs "
+                "that were searched again")
+    if args.rescore_dir is not None and args.skip_existing:
+        p.error("--rescore_dir cannot be combined with --skip_existing: a skipped pair has no costs to price a path with")
     if args.concat_max_num is not None and not 1 <= args.concat_max_num <= 8:
         p.error("--concat_max_num must be 1 .. 8")
     if args.min_dur is not None and args.min_dur < 0:
@@ -170,6 +191,11 @@ def frames_wanted(args) -> bool:
 def prior_path(args, p) -> Path:
     """--prior_dir: the prior alignment file of a pair, named like its output file."""
     return Path(args.prior_dir) / f"{args.src_lang}-{args.tgt_lang}" / os.path.basename(p.output_path)
+
+
+def rescore_path(args, p) -> Path:
+    """--rescore_dir: the given alignment file of a pair, named like its output file."""
+    return Path(args.rescore_dir) / f"{args.src_lang}-{args.tgt_lang}" / os.path.basename(p.output_path)
 
 
 def post_chain_wanted(args) -> bool:
@@ -375,7 +401,16 @@ def _prepare_pair(p: VecalignData, args, src_k: int, tgt_k: int):
     if getattr(args, "prior_dir", None) is not None:
         from ..utils.file_utils import read_alignments
         pr = read_alignments(prior_path(args, p))
-    return st, tt, se, te, fr, pr
+    given = None   # --rescore_dir: None (no file), ("ok", the complete path) or ("invalid", why)
+    if getattr(args, "rescore_dir", None) is not None and check_exist(rescore_path(args, p)):
+        from ..utils.file_utils import read_alignments
+        from ..vecalign.dp_utils import complete_alignments
+        try:
+            given = ("ok", complete_alignments(read_alignments(rescore_path(args, p)), int(st.shape[1]), int(tt.shape[1])))
+        except ValueError as e:
+            logger.warning(f"--rescore_dir: {rescore_path(args, p)} is no monotone alignment and is not priced: {e}")
+            given = ("invalid", str(e))
+    return st, tt, se, te, fr, pr, given
 
 
 def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Optional[int] = None, stats: Optional[dict] = None):
@@ -444,6 +479,20 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
                 else:
                     vals = pb.h_contact.numpy()[i].tolist() + [0, 2 * int(pb.width_over2)]
                 contact_lines.append("\t".join([s, t] + [str(v) for v in vals]) + "\n")
+        if rescore_tsv is not None:
+            from ..vecalign.dp_utils import search_error
+            h = None if getattr(pb, "h_given", None) is None else [x.numpy() for x in pb.h_given]
+            for i, p in enumerate(chunk):
+                given = held[0][i][6]
+                if given is None:
+                    continue
+                s, t = os.path.basename(p.src_seg_path), os.path.basename(p.tgt_seg_path)
+                if given[0] != "ok":
+                    rescore_lines.append("\t".join([s, t, "invalid"] + [""] * 11) + "\n")
+                    continue
+                found, got, rep = float(h[0][i, 0]), float(h[1][i, 0]), h[2][i].tolist()
+                rescore_lines.append("\t".join([s, t, search_error(found, got, rep), "%.6f" % found, "%.6f" % got, "%.6f" % float(h[1][i, 1])]
+                                               + [str(int(v)) for v in rep]) + "\n")
         if margin is not None:
             margin.collect(chunk, pb, info, align, offs)
         writes = []
@@ -461,6 +510,7 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
     contact_tsv = getattr(args, "contact_tsv", None)
     guard = int(getattr(args, "widen_guard", 0))
     widened, touching, contact_lines = [0], [0], []
+    rescore_tsv, rescore_lines = getattr(args, "rescore_tsv", None), []
     bar = my_tqdm(total=len(todo))
     try:
         submit_more()
@@ -471,12 +521,12 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
             # ---- uploads on the copy stream (pinned -> device), then gather + align on the compute stream
             with torch.cuda.stream(copy_stream):
                 dev_in = [(torch.from_numpy(st).to(dev, non_blocking=True), torch.from_numpy(tt).to(dev, non_blocking=True),
-                           se.to(dev, non_blocking=True), te.to(dev, non_blocking=True)) for st, tt, se, te, _, _ in prepared]
+                           se.to(dev, non_blocking=True), te.to(dev, non_blocking=True)) for st, tt, se, te, _, _, _ in prepared]
                 up = torch.cuda.Event()
                 up.record(copy_stream)
             compute.wait_event(up)
             docs = []
-            for (st, tt, se, te, _, _), (dst, dtt, dse, dte) in zip(prepared, dev_in):
+            for (st, tt, se, te, _, _, _), (dst, dtt, dse, dte) in zip(prepared, dev_in):
                 for x in (dst, dtt, dse, dte):
                     x.record_stream(compute)
                 sv, tv = gather_candidates(dse, dst), gather_candidates(dte, dtt)
@@ -514,6 +564,15 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
                     contact = pb.band_contact(0, guard)
                     pb.h_contact = torch.empty(contact.shape, dtype=contact.dtype, pin_memory=True)
                     pb.h_contact.copy_(contact, non_blocking=True)   # (lands before the event of fetch_async)
+            if rescore_tsv is not None and any(q[6] is not None and q[6][0] == "ok" for q in prepared):
+                # two calls behind run(): the returned paths' totals, then the given paths'; read back with the results
+                ok = [q[6] is not None and q[6][0] == "ok" for q in prepared]
+                own = pb.score_alignments(["own" if k else None for k in ok])
+                got = pb.score_alignments([q[6][1] if k else None for q, k in zip(prepared, ok)])
+                pb.h_given = tuple(torch.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in (own.total, got.total, got.report))
+                for hx, dx in zip(pb.h_given, (own.total, got.total, got.report)):
+                    hx.copy_(dx, non_blocking=True)
+                pb.given_keep = (own, got)
             if margin is not None:
                 margin.gather(pb)
             ev = pb.fetch_async()
@@ -557,6 +616,9 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
     if contact_tsv is not None:
         shard = "" if getattr(args, "n_shard", 1) <= 1 else f".{args.rank}"   # (one file per rank: the ranks do not communicate)
         _write_text(contact_tsv + shard, "".join(contact_lines))
+    if rescore_tsv is not None:
+        shard = "" if getattr(args, "n_shard", 1) <= 1 else f".{args.rank}"   # (one file per rank, like --contact_tsv)
+        _write_text(rescore_tsv + shard, "".join(rescore_lines))
     if widen or contact_tsv is not None:
         logger.info(f"band contact: {touching[0]} of {len(todo)} pairs touch the edge of their final band"
                     + (f", {widened[0]} were searched again in a wider band" if widen else ""))

@@ -94,6 +94,87 @@ def prior_rows_from_alignments(alignments):
     return rows
 
 
+def complete_alignments(alignments, n, m):
+    """[(x ids, y ids)] in document order, as read_alignments returns them, possibly with gaps -> the complete monotone
+    list over n x m segments: every segment no line names becomes a unit deletion ([i], []) / ([], [j]) in front of the
+    line that follows it (source side first), and a one-sided line of several segments is split into unit deletions --
+    what svx_score_alignments prices (include/svx.h).  Lines with both sides are kept as they are, whatever their size.
+    Raises ValueError naming the line (from 1) when a side is not a contiguous ascending run, runs backwards, or leaves
+    the document."""
+    out, cx, cy = [], 0, 0
+    for no, (x, y) in enumerate(alignments, 1):
+        x, y = [int(v) for v in x], [int(v) for v in y]
+        for name, ids, cur, size in (("source", x, cx, n), ("target", y, cy, m)):
+            if any(b != a + 1 for a, b in zip(ids, ids[1:])):
+                raise ValueError("line %d: the %s side %s is not a contiguous ascending run" % (no, name, ids))
+            if ids and ids[0] < cur:
+                raise ValueError("line %d: the %s side %s runs backwards (segment %d is already aligned)" % (no, name, ids, ids[0]))
+            if ids and ids[-1] >= size:
+                raise ValueError("line %d: the %s side %s leaves the document (%d segments)" % (no, name, ids, size))
+        if not x and not y:
+            raise ValueError("line %d: both sides are empty" % no)
+        out += [([i], []) for i in range(cx, x[0] if x else cx)]
+        out += [([], [j]) for j in range(cy, y[0] if y else cy)]
+        if x and y:
+            out.append((x, y))
+        else:
+            out += [([i], []) for i in x] + [([], [j]) for j in y]
+        cx, cy = (x[-1] + 1 if x else cx), (y[-1] + 1 if y else cy)
+    out += [([i], []) for i in range(cx, n)]
+    out += [([], [j]) for j in range(cy, m)]
+    return out
+
+
+def given_rows_from_alignments(alignments):
+    """[(x ids, y ids)] -> int32 [r, 4] rows (x_start, x_len, y_start, y_len) for svx_score_alignments: the start of a
+    non-empty side is its first id, that of an empty side the end of the row before (so a complete path chains)."""
+    rows = np.zeros((len(alignments), 4), dtype=np.int32)
+    xe = ye = 0
+    for i, (x, y) in enumerate(alignments):
+        xs, ys = (int(x[0]) if len(x) else xe), (int(y[0]) if len(y) else ye)
+        rows[i] = (xs, len(x), ys, len(y))
+        xe, ye = xs + len(x), ys + len(y)
+    return rows
+
+
+REPORT_FIELDS = ("rows", "priced", "deletions", "wide", "invalid", "off_type", "outside", "complete")
+
+
+def search_error(found_total, given_total, given_report):
+    """The verdict of search-error analysis for one pair: "unpriced" when the given path has a row
+    without a price or is no complete path (wide > 0, invalid > 0 or complete == 0 in its svx_score_alignments report),
+    "search" when it is cheaper than the path the DP returned (the search missed it), "model" otherwise (the model
+    prefers the returned path: no band width will find the given one).  A plain comparison of two doubles."""
+    rep = [int(v) for v in given_report]
+    if rep[3] > 0 or rep[4] > 0 or rep[7] != 1:
+        return "unpriced"
+    return "search" if float(given_total) < float(found_total) else "model"
+
+
+class GivenScores:
+    """What PreparedBatch.score_alignments() left on the device: scores [sum of caps] float64, total [pairs, 2] float64,
+    report [pairs, 8] int32 and the row offsets of the pairs in `scores`; skipped[i]: pair i was not scored; cgiven: the
+    svx_given array of the call (profiles/given_bench.py repeats the call with it)."""
+
+    def __init__(self, scores, total, report, offs, skipped, keep, cgiven=None):
+        self.scores, self.total, self.report, self.offs, self.skipped = scores, total, report, offs, skipped
+        self._keep, self.cgiven = keep, cgiven
+
+    def fetch(self):
+        """-> per pair None (skipped) or dict(report (8 ints, REPORT_FIELDS), total, del_penalty, scores [rows]); the
+        copies are the only synchronisation."""
+        total, report, scores = self.total.cpu().numpy(), self.report.cpu().numpy(), self.scores.cpu().numpy()
+        out = []
+        for i, skip in enumerate(self.skipped):
+            if skip:
+                out.append(None)
+                continue
+            o, cnt = int(self.offs[i]), max(0, int(report[i, 0]))
+            out.append(dict(report=tuple(int(v) for v in report[i]), total=float(total[i, 0]), del_penalty=float(total[i, 1]),
+                            scores=scores[o:o + cnt].copy()))
+        return out
+
+
 def prior_width(rows_or_alignments, n, m):
     """Host twin of svx_prior_width (include/svx.h): the width_over2 from which the band around a prior holds every node
     of every block of that prior -- 1 + max over the ingested rows, the remainder row included, of min(x_len, y_len),
@@ -423,6 +504,66 @@ class PreparedBatch:
         ctx.check(ctx.lib.svx_band_contact(ctx.h, int(level), int(guard), _p(out)))
         return out
 
+    def score_alignments(self, given):
+        """svx_score_alignments for the last run() on the context (include/svx.h): price given alignments with that
+        call's normalisers, deletion penalty, band and type set.  given: one entry per pair -- a list of (x ids, y ids)
+        (given_rows_from_alignments; complete_alignments() fills a file's gaps first), an int [rows, 4] array of
+        (x_start, x_len, y_start, y_len), None to skip the pair, or "own" for the batch's own result, whose total is the
+        cost of the path the DP returned.  -> GivenScores (device tensors; .fetch() reads them back).  Asynchronous on the
+        current stream: host rows travel through pinned memory, nothing waits for the device."""
+        ctx = self.ctx
+        t = ctx.torch
+        npairs = len(self.vecs)
+        if len(given) != npairs:
+            raise ValueError("score_alignments: one entry per document pair (%d given, %d pairs)" % (len(given), npairs))
+        ctx.use_current_stream()
+        host, caps = [], []
+        for i, g in enumerate(given):
+            if g is None or (isinstance(g, str) and g == "own"):
+                host.append(None)
+                caps.append(0 if g is None else int(self.offs[i + 1] - self.offs[i]))
+                continue
+            if isinstance(g, str):
+                raise ValueError("score_alignments: pair %d: %r (only the string 'own' is known)" % (i, g))
+            rows = np.asarray(g) if isinstance(g, np.ndarray) or t.is_tensor(g) else None
+            if rows is None:
+                rows = given_rows_from_alignments(g)
+            elif rows.ndim != 2 or rows.shape[1] != 4 or rows.dtype.kind not in "iu":
+                raise ValueError("score_alignments: pair %d: rows must be an int [rows, 4] array" % i)
+            host.append(np.ascontiguousarray(rows, dtype=np.int32))
+            caps.append(len(rows))
+        offs = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+        scores = t.full((max(1, int(offs[-1])),), float("nan"), dtype=t.float64, device=ctx.tdev)
+        total = t.full((npairs, 2), float("nan"), dtype=t.float64, device=ctx.tdev)
+        report = t.zeros((npairs, 8), dtype=t.int32, device=ctx.tdev)
+        n_host = int(sum(len(h) for h in host if h is not None))
+        h_rows = t.zeros((max(1, n_host), 4), dtype=t.int32, pin_memory=True)
+        h_info = t.zeros((npairs, 2), dtype=t.int32, pin_memory=True)
+        at, starts = 0, []
+        for i, h in enumerate(host):
+            starts.append(at)
+            if h is not None:
+                h_rows.numpy()[at:at + len(h)] = h
+                h_info.numpy()[i, 0] = len(h)
+                at += len(h)
+        d_rows = h_rows.to(ctx.tdev, non_blocking=True)
+        d_info = h_info.to(ctx.tdev, non_blocking=True)
+        cg = (_lib.Given * npairs)()
+        for i, g in enumerate(given):
+            c = cg[i]
+            if g is None:
+                continue
+            if host[i] is None:   # "own"
+                c.rows, c.info = self.align.data_ptr() + 16 * int(self.offs[i]), self.info.data_ptr() + 8 * i
+            else:
+                c.rows, c.info = d_rows.data_ptr() + 16 * starts[i], d_info.data_ptr() + 8 * i
+            c.cap = caps[i]
+            c.scores = scores.data_ptr() + 8 * int(offs[i])
+            c.total = total.data_ptr() + 16 * i
+            c.report = report.data_ptr() + 32 * i
+        ctx.check(ctx.lib.svx_score_alignments(ctx.h, cg, npairs))
+        return GivenScores(scores, total, report, offs, [g is None for g in given], (h_rows, h_info, d_rows, d_info, self), cg)
+
     def run_widen(self, guard=0, max_width_over2=None, max_rounds=4):
         """run() followed by band doubling (svx_align_widen, include/svx.h): pairs whose path touches the band edge are
         searched again around that path in twice the band, up to `max_rounds` times and `max_width_over2` (default:
@@ -645,13 +786,18 @@ def align_batch(pairs, final_alignment_types, del_percentile_frac, width_over2, 
 
 def vecalign(vecs0, vecs1, final_alignment_types, del_percentile_frac, width_over2, max_size_full_dp,
              costs_sample_size, num_samps_for_norm, norms0=None, norms1=None, normalize_inputs_inplace=False,
-             full_stack=False):
+             full_stack=False, given=None, search="coarse_to_fine"):
     """dp_utils.py:381-537.  Returns {0: {'final_alignments', 'alignment_scores', 'del_penalty',
     'size0', 'size1', 'alignment_types'}, d: {'del_penalty', 'size0', 'size1'} ...}; with full_stack=True every
     depth also carries the intermediates the reference keeps (n0, n1, searchpath, a_b_costs, b_offset, a_b_csum,
-    a_b_xp, a_b_yp, new_b_offset, alignments: PreparedBatch.level_stack), copied back from the device."""
+    a_b_xp, a_b_yp, new_b_offset, alignments: PreparedBatch.level_stack), copied back from the device.
+    given: alignments [(x ids, y ids)] (or int rows [r, 4]) to price with this call's costs (svx_score_alignments); then
+    stack[0]['given'] = dict(verdict, found_total, given_total, del_penalty, report, scores) (search_error()).
+    search: "coarse_to_fine" (the reference) or "straight" (PreparedBatch: depth 0 only)."""
+    if search != "coarse_to_fine":
+        max_size_full_dp = 1 << 30
     pb = PreparedBatch([(vecs0, vecs1)], final_alignment_types, del_percentile_frac, width_over2, max_size_full_dp,
-                       costs_sample_size, num_samps_for_norm, norms=[(norms0, norms1)])
+                       costs_sample_size, num_samps_for_norm, norms=[(norms0, norms1)], search=search)
     timed = logger.isEnabledFor(logging.INFO)
     if timed:
         pb.ctx.check(pb.ctx.lib.svx_set_profiling(pb.ctx.h, 1))
@@ -672,6 +818,12 @@ def vecalign(vecs0, vecs1, final_alignment_types, del_percentile_frac, width_ove
             stack[depth].update(pb.level_stack(0, depth))
     stack[0]['final_alignments'] = alignments
     stack[0]['alignment_scores'] = scores
+    if given is not None:
+        own, got = pb.score_alignments(["own"]), pb.score_alignments([given])
+        own, got = own.fetch()[0], got.fetch()[0]
+        stack[0]['given'] = dict(verdict=search_error(own['total'], got['total'], got['report']), found_total=own['total'],
+                                 given_total=got['total'], del_penalty=got['del_penalty'], report=got['report'],
+                                 scores=got['scores'])
     if normalize_inputs_inplace:
         make_norm1(vecs0)
         make_norm1(vecs1)

@@ -15,7 +15,7 @@ from typing import List, Optional, Set, Tuple, Union
 
 from ..utils.embedding_utils import make_doc_embedding, read_in_embeddings
 from ..utils.file_utils import read_alignments
-from .dp_utils import vecalign
+from .dp_utils import complete_alignments, vecalign
 
 logger = logging.getLogger("vecalign")
 logger.propagate = False
@@ -140,11 +140,24 @@ def align(src: str, tgt: str, src_embed: List[str], src_stopes: bool, tgt_stopes
     if src_vectors.dtype != tgt_vectors.dtype:
         src_vectors, tgt_vectors = src_vectors.float(), tgt_vectors.float()
     logger.info(f'Aligning src={src} to tgt={tgt}')
+    gold, gold_path = None, None
+    if gold_alignment is not None:
+        gold = read_alignments(gold_alignment)
+        try:   # the gold path at the aligner's prices (svx_score_alignments): logged behind the P/R/F below
+            gold_path = complete_alignments(gold, int(src_vectors.shape[1]), int(tgt_vectors.shape[1]))
+        except ValueError as e:
+            logger.warning('gold alignment %s is no monotone path and is not priced: %s', gold_alignment, e)
     if mode == "ref":
         stack = vecalign(vecs0=src_vectors, vecs1=tgt_vectors, final_alignment_types=types,
                          del_percentile_frac=del_percentile_frac, width_over2=width_over2,
                          max_size_full_dp=max_size_full_dp, costs_sample_size=costs_sample_size,
-                         num_samps_for_norm=num_samps_for_norm, full_stack=bool(debug_save_stack))
+                         num_samps_for_norm=num_samps_for_norm, full_stack=bool(debug_save_stack), given=gold_path)
+    elif gold_path is not None:
+        w2 = max(3, (band + 1) // 2) if mode == "band" else max(int(src_vectors.shape[1]), int(tgt_vectors.shape[1])) + 1
+        stack = vecalign(vecs0=src_vectors, vecs1=tgt_vectors, final_alignment_types=types,
+                         del_percentile_frac=del_percentile_frac, width_over2=w2, max_size_full_dp=max_size_full_dp,
+                         costs_sample_size=costs_sample_size, num_samps_for_norm=num_samps_for_norm, given=gold_path,
+                         search="straight")
     else:
         from .dp_utils import align_band
         w2 = max(3, (band + 1) // 2) if mode == "band" else max(int(src_vectors.shape[1]), int(tgt_vectors.shape[1])) + 1
@@ -162,8 +175,13 @@ def align(src: str, tgt: str, src_embed: List[str], src_stopes: bool, tgt_stopes
         pickle.dump(stack, open(debug_save_stack, mode="wb"))
     if gold_alignment is not None:
         from .score import log_final_scores, score_multiple
-        res = score_multiple(gold_list=[read_alignments(gold_alignment)], test_list=[stack[0]['final_alignments']])
+        res = score_multiple(gold_list=[gold], test_list=[stack[0]['final_alignments']])
         log_final_scores(res)
+        g = stack[0].get('given')
+        if g is not None:
+            logger.info('gold path at the aligner\'s prices: verdict %s, found total %.6f, gold total %.6f, deletion penalty %.6f, '
+                        '(rows, priced, deletions, wide, invalid, off_type, outside, complete) = %s',
+                        g['verdict'], g['found_total'], g['given_total'], g['del_penalty'], tuple(g['report']))
     return stack
 
 
