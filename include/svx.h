@@ -620,6 +620,77 @@ typedef struct svx_given {
 } svx_given;
 int svx_score_alignments(svx_ctx *ctx, const svx_given *given /* HOST [n_pairs] */, int n_pairs);
 
+/* ---- row slack: how decided is each returned row? (csrc/svx_slack.hip) ------------------------------
+ * The entries above judge a whole path.  The slack of a returned row is the min-marginal of the band DP: the total of the
+ * best path of the SAME search space that does not contain the row, minus the total of the returned path.  0: there is a
+ * second optimum and the row was picked by the tie rule (first strictly smaller candidate, dp_core.pyx); small: the row is
+ * ambiguous; several deletion penalties: the row is solid.  ("Margin" is the k-NN ratio margin in this library; this
+ * figure is called slack.)
+ *
+ * Notation of svx_sparse_dp (dp_core.pyx:269-404): A rows of the cost tensor, B cells per diagonal, bout = b_offset_out
+ * (bout[0] = bout[1] = b_offset_in[0], bout[a] = b_offset_in[a-2] + 1), xs / ys = x_in_size / y_in_size, moves in list
+ * order = the T types (xo, yo), then (0,1), then (1,0), st = xo + yo.
+ * Cells.  Cell (a, b), 0 <= a < A+2, 0 <= b < B, is the node (x, y) = (a - y, b + bout[a]); its kind, tested in this order:
+ *   border-x  x == 0 and 0 <= y <= ys;   border-y  y == 0 and 0 <= x <= xs;
+ *   general   1 <= x <= xs, 1 <= y <= ys and a - 2 < A;   outside  anything else.
+ * Edges E: exactly what the forward loop relaxes.  For every general cell v = (a, b) and move t, with ap = a - st and the
+ *   predecessor (x - xo, y - yo): when ap >= 0, x - xo >= 0, y - yo >= 0 and bp = (y - yo) - bout[ap] is in [0, B) there is
+ *   an edge (ap, bp) -> (a, b) of weight (double) costs[t][a-2][b] for t < T and del_penalty for the two deletions.
+ * Border edges E_b: what the traceback walks along the closed-form borders, weight del_penalty: (0, y) -> (0, y+1) when
+ *   both are band cells of kind border-x, (x, 0) -> (x+1, 0) when both are band cells of kind border-y, and (0,0) -> (1,0)
+ *   from the border-x cell (0,0) to a border-y cell.
+ * Forward value F(cell): the csum the forward DP stored (borders closed form, +inf unreachable); nothing is recomputed.
+ * Backward value Bk: Bk(end) = 0 for the end cell (xs + ys, ys - bout[xs + ys]); every other border or general cell u has
+ *   Bk(u) = min over the edges u -> v of E and E_b of (w + Bk(v)), each candidate ONE float64 addition, +inf when there is no
+ *   edge; outside cells are +inf; when the end cell is no band cell every value is +inf.  A minimum of singly rounded sums
+ *   does not depend on the order of evaluation: Bk is the same bits from run to run and kernel to kernel.
+ * Slack of row r = (x_start, x_len, y_start, y_len): its edge e* goes from u* = (x_start, y_start) to v* = (x_start + x_len,
+ *   y_start + y_len) by move (x_len, y_len).  With c = x_start + y_start, the edges with a(u) <= c < a(v) cross the cut
+ *   behind diagonal c, and every path crosses it by exactly one of them.
+ *     alt[r]   = min over the crossing edges e != e* of ((F(u) + w) + Bk(v)), in that order; +inf when there is none
+ *     slack[r] = alt[r] - total,   total = F(end) (+inf when the end cell is no band cell: the difference is then NaN)
+ *   Not clamped.  In exact arithmetic slack >= 0; in float64 it may be negative by rounding, by at most
+ *   2 (A+2) 2^-53 max|finite csum|.  A row that is no edge of E or E_b -- a negative field, a node off the lattice or off
+ *   the band, a move that is neither a type of the list nor a deletion -- gets NaN and is never used to form an address:
+ *   row fields may hold anything.  (The DP's own rows are always edges.)
+ * A known corner: a border cell keeps its closed-form F even when its border predecessor is no band cell; the reference's
+ *   traceback fails on such a path ('traceback bug').  Slack uses the stored F as it is.
+ *
+ * svx_sparse_dp_backward: the arguments and limits of svx_sparse_dp (costs [T][A][B], A, B >= 1, T <= SVX_MAX_TYPES, type
+ *   sizes 1..100; sizes >= 0); writes bsum [A+2][B] = Bk.  One launch, one workgroup: B <= 64 and steps <= 120 take the
+ *   LDS-staged sweep, anything else the strided kernel (Bk ring in LDS while it fits 150 KB, else re-read from bsum).
+ * svx_path_slack: the slack kernel of svx_row_slack on caller-supplied planes csum, bsum [A+2][B] (device), any B.
+ *   rows (device [cap][4], 16-byte aligned), n_rows (device [1]; clamped to [0, cap]); slack[r] is written for r < n_rows,
+ *   nothing past that.  One launch.  Reads costs, b_offset_in, the two planes and the rows.
+ * Both return SVX_ERR_ARG with text for a null argument, A or B < 1, a negative size, a bad type list, rows not 16-byte
+ * aligned, a negative cap; asynchronous on the context's stream. */
+int svx_sparse_dp_backward(svx_ctx *ctx, const float *costs, const int32_t *b_offset_in, int A, int B,
+                           const int32_t *types_host, int T, double del_penalty, int x_in_size, int y_in_size,
+                           double *bsum /* [A+2][B] */);
+int svx_path_slack(svx_ctx *ctx, const float *costs, const int32_t *b_offset_in, int A, int B, const int32_t *types_host,
+                   int T, double del_penalty, int x_in_size, int y_in_size, const double *csum, const double *bsum,
+                   const int32_t *rows /* [n_rows][4] */, const int32_t *n_rows /* device [1] */, int cap,
+                   double *slack /* [cap] */);
+
+/* svx_row_slack: the slack of every returned row at level 0 of the LAST svx_align_batch / svx_align_around call on the
+ * context, under the rules of svx_band_contact and svx_score_alignments: both halves of a pipelined call, in the pair
+ * order of svx_debug_level; n_pairs must equal that call's pair count; svx_flush first; asynchronous on the context's
+ * stream, no host synchronisation.  It reads what the call's arena still holds of level 0 and svx_debug_level exposes --
+ * the level's own rows and their count, a_b_costs, a_b_csum, b_offset / new_b_offset, the penalty, the sizes, the band and
+ * the call's type set -- fp32 costs and fp64 sums that are resident; no embedding row is read again.
+ * slack (HOST [n_pairs] of device [n + m + 2] double): slack[p][r] is written for r < the pair's row count, nothing past
+ *   that.  slack[p] == NULL skips the pair: nothing of it is written.
+ * summary (device [n_pairs][4] int32, 16-byte aligned) = (rows, rows with slack == 0, rows with slack == +inf, 0).
+ * A pair with info[1] != 0 gets summary = (-1, -1, -1, -1); its slack is untouched.
+ * SVX_ERR_ARG with text, nothing queued: a call that ran the tile sweep, which keeps no cost array (a_b_costs is NULL: a
+ * band above 64 cells in the straight and around-wide modes); no earlier successful call; a pair count that differs; a
+ * null slack / summary; summary not 16-byte aligned; a negative n_pairs.
+ * Two launches, one workgroup per pair each: the backward sweep into a Bk plane, then the slack kernel over it.  The
+ * scratch -- the descriptors and one plane of (path capacity + 2) x B doubles per pair -- is the context's
+ * post-processing scratch (svx_scratch_bytes). */
+int svx_row_slack(svx_ctx *ctx, double *const *slack /* HOST [n_pairs] of device [n+m+2] */,
+                  int32_t *summary /* device [n_pairs][4], 16-byte aligned */, int n_pairs);
+
 /* Per-level intermediates of the LAST svx_align_batch call on this context -- the entries of the `stack` the reference
  * returns (dp_utils.py:412-537) -- as device pointers into the context's scratch arena (valid until the next call;
  * the scalar fields are read back, which synchronises the stream).  Pointers are NULL for what a level does not have

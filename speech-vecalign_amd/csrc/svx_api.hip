@@ -457,6 +457,32 @@ int svx_sparse_dp(svx_ctx* ctx, const float* costs, const int32_t* b_offset_in, 
     return svxl_sparse_dp(ctx, costs, b_offset_in, A, B, ty, del_penalty, x_in_size, y_in_size, csum, xp, yp, b_offset_out);
 }
 
+int svx_sparse_dp_backward(svx_ctx* ctx, const float* costs, const int32_t* b_offset_in, int A, int B, const int32_t* types_host,
+                           int T, double del_penalty, int x_in_size, int y_in_size, double* bsum) {
+    NEED(ctx, ctx && b_offset_in && bsum && (costs || T == 0), "svx_sparse_dp_backward: null argument");
+    NEED(ctx, A >= 1 && B >= 1, "svx_sparse_dp_backward: empty cost band");
+    NEED(ctx, x_in_size >= 0 && y_in_size >= 0, "svx_sparse_dp_backward: negative document size");
+    SvxTypes ty;
+    int rc = make_types(ctx, types_host, T, &ty);
+    if (rc) return rc;
+    return svxl_sparse_dp_backward(ctx, costs, b_offset_in, A, B, ty, del_penalty, x_in_size, y_in_size, bsum);
+}
+
+int svx_path_slack(svx_ctx* ctx, const float* costs, const int32_t* b_offset_in, int A, int B, const int32_t* types_host, int T,
+                   double del_penalty, int x_in_size, int y_in_size, const double* csum, const double* bsum, const int32_t* rows,
+                   const int32_t* n_rows, int cap, double* slack) {
+    NEED(ctx, ctx && b_offset_in && csum && bsum && n_rows && (costs || T == 0), "svx_path_slack: null argument");
+    NEED(ctx, cap >= 0 && ((rows && slack) || cap == 0), "svx_path_slack: cap %d with null rows / slack", cap);
+    NEED(ctx, aligned16(rows), "svx_path_slack: rows must be 16-byte aligned");
+    NEED(ctx, A >= 1 && B >= 1, "svx_path_slack: empty cost band");
+    NEED(ctx, x_in_size >= 0 && y_in_size >= 0, "svx_path_slack: negative document size");
+    SvxTypes ty;
+    int rc = make_types(ctx, types_host, T, &ty);
+    if (rc) return rc;
+    if (cap == 0) return SVX_OK;
+    return svxl_path_slack(ctx, costs, b_offset_in, A, B, ty, del_penalty, x_in_size, y_in_size, csum, bsum, rows, n_rows, cap, slack);
+}
+
 int svx_make_norm1(svx_ctx* ctx, float* vecs, int64_t rows, int d) {
     NEED(ctx, ctx && (vecs || rows == 0), "svx_make_norm1: null argument");
     int rc = check_dim(ctx, d);

@@ -255,7 +255,9 @@ struct svx_ctx {
     // whole buffer anew: svx_alignment_rows and svx_concat_rows (svx_alignrows.hip: descriptors, chunk table, counts,
     // offsets, compacted rows), svx_knn_search_groups (svx_groupsearch.hip: offsets, workgroup table) and svx_time_prior
     // (svx_prior.hip: descriptors, prefix counts), svx_band_contact and svx_align_widen (svx_contact.hip: descriptors, the
-    // report rows, the staged priors of a round).  They go through svxl_scratch_begin / svxl_scratch_upload only.
+    // report rows, the staged priors of a round), svx_score_alignments (svx_given.hip: descriptors, chunk table, partial sums)
+    // and svx_row_slack (svx_slack.hip: descriptors, one backward plane per pair).  They go through svxl_scratch_begin /
+    // svxl_scratch_upload only.
     char* post_buf;
     size_t post_bytes;        // counted in svx_scratch_bytes
     char* post_pin[2];
@@ -340,3 +342,8 @@ int svxl_prior_ingest_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs);
 bool svxl_last_batch(svx_ctx*, const SvxPairDev** host, int* n_pairs, int* band);
 // storage type, embedding dimension and level-0 type set of that same call (svx_given.hip); false when there is none
 bool svxl_last_batch_types(svx_ctx*, int* dtype, int* d, const SvxTypes** types);
+// row slack (svx_slack.hip): the backward band DP and the slack of the rows of a path, per-op
+int svxl_sparse_dp_backward(svx_ctx*, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen,
+                            int xs, int ys, double* bsum);
+int svxl_path_slack(svx_ctx*, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen, int xs,
+                    int ys, const double* csum, const double* bsum, const int* rows, const int* n_rows, int cap, double* slack);

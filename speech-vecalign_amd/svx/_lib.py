@@ -117,6 +117,10 @@ _SIGS = {
                                  ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_vp, c_vp]),
     "svx_sparse_dp": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_f64, c_int, c_int,
                               c_vp, c_vp, c_vp, c_vp]),
+    "svx_sparse_dp_backward": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_f64, c_int, c_int,
+                                       c_vp]),
+    "svx_path_slack": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_f64, c_int, c_int,
+                               c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "svx_make_norm1": (c_int, [c_vp, c_vp, c_i64, c_int]),
     "svx_downsample": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "svx_compute_norms": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp]),
@@ -153,6 +157,7 @@ _SIGS = {
     "svx_align_widen": (c_int, [c_vp, ctypes.POINTER(AlignParams), ctypes.POINTER(Pair), ctypes.POINTER(Prior), c_int,
                                 ctypes.POINTER(WidenParams), c_vp]),
     "svx_score_alignments": (c_int, [c_vp, ctypes.POINTER(Given), c_int]),
+    "svx_row_slack": (c_int, [c_vp, ctypes.POINTER(c_vp), c_vp, c_int]),
     "svx_alignment_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), c_int, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "svx_concat_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), ctypes.POINTER(Frames), c_int, ctypes.POINTER(ConcatParams), c_i64,
                                 c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),

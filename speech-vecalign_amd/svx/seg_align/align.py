@@ -36,6 +36,12 @@ alignment file DIR/{src}-{tgt}/{s}-{t}.txt (gold, an earlier run, another tool's
 normalisers and the deletion penalty this run used (svx_score_alignments) and compared with the total of the path the DP
 returned: `search` when the given path is cheaper (the search missed it), `model` when it is dearer (no band will find it),
 `unpriced` when a row of it has no price.  The alignment files do not change.
+
+--slack_dir DIR says how DECIDED each returned row is, which its cost does not: DIR/{src}-{tgt}/{s}-{t}.txt holds the job's
+own alignment lines with a fourth field, the row's slack (svx_row_slack) -- the total of the best path of the same band that
+does not contain the row, minus the total of the returned path: `[0, 1]:[0]:0.349737:0.012345`.  0 means a second optimum
+exists and the tie rule picked the row; a small value means the row is ambiguous (a repeated phrase, near-silent segments);
+several deletion penalties mean it is solid; `inf` means no other path exists in the band.  The alignment files do not change.
 """
 import argparse
 import dataclasses
@@ -116,6 +122,11 @@ def parse_args(argv=None):
                         "wide invalid off_type outside complete' (tab-separated): verdict search = the given path is cheaper than the "
                         "returned one, model = it is dearer, unpriced = it has rows without a price or is no complete path, invalid = "
                         "the file is no monotone alignment (the numbers are then empty)")
+    p.add_argument("--slack_dir", type=str, default=None,
+                   help="also write {slack_dir}/{src}-{tgt}/{s}-{t}.txt: the alignment lines with a fourth field, the row's slack "
+                        "(svx_row_slack): best total of a path of the same band without the row minus the returned path's total, "
+                        "%%.6f; 0 = tied with another optimum, inf = no other path.  Needs the band's cost array: not for bands above "
+                        "64 cells in --mode band / dense / --prior_band (the tile sweep keeps none)")
     p.add_argument("--batch_size", type=int, default=32, help="document pairs per device pass")
     p.add_argument("--io_threads", type=int, default=None, help="host threads that parse / read ahead of the GPU (default: the CPU count, at most 32)")
     p.add_argument("--seed", type=int, default=None, help="derive one sampling stream per pair from (seed, pair index)")
@@ -164,6 +175,16 @@ def parse_args(argv=None):
                 "that were searched again")
     if args.rescore_dir is not None and args.skip_existing:
         p.error("--rescore_dir cannot be combined with --skip_existing: a skipped pair has no costs to price a path with")
+    if args.slack_dir is not None:
+        if args.widen:
+            p.error("--slack_dir cannot be combined with --widen: after band doubling the last device call holds only the pairs "
+                    "that were searched again")
+        if args.skip_existing:
+            p.error("--slack_dir cannot be combined with --skip_existing: a skipped pair has no costs to measure slack with")
+        cells = 2 * max(3, (args.band + 1) // 2) if args.mode == "band" else (args.prior_band if args.mode == "around" else None)
+        if cells is not None and cells > 64:   # (--mode dense: the band follows the documents; the library refuses it)
+            p.error(f"--slack_dir needs the band's cost array: a band of {cells} cells runs the tile sweep, which keeps no cost "
+                    "array (at most 64 cells in --mode band and with --prior_band)")
     if args.concat_max_num is not None and not 1 <= args.concat_max_num <= 8:
         p.error("--concat_max_num must be 1 .. 8")
     if args.min_dur is not None and args.min_dur < 0:
@@ -285,6 +306,17 @@ def _write_result(path: str, rows: np.ndarray, scores: np.ndarray):
     with open(tmp, "wb") as fp:  # write-then-rename, the repo's crash-safety idiom
         fp.write(format_alignment_rows(rows, scores))
     Path(tmp).replace(path)
+
+
+def format_slack_lines(rows: np.ndarray, scores: np.ndarray, slack: np.ndarray) -> str:
+    """--slack_dir: the lines of the alignment file, each with ':%.6f' of the row's slack behind it ('inf' for +inf)."""
+    lines = format_alignment_rows(rows, scores).decode().splitlines()
+    assert len(lines) == len(slack), f"{len(lines)}, {len(slack)}"
+    return "".join("%s:%.6f\n" % (ln, float(v)) for ln, v in zip(lines, slack))
+
+
+def _write_slack(path: str, rows: np.ndarray, scores: np.ndarray, slack: np.ndarray):
+    _write_text(path, format_slack_lines(rows, scores, slack))
 
 
 def _write_post(path: str, rows: np.ndarray, scores: np.ndarray, frames, max_cost, chain: dict):
@@ -435,6 +467,10 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
     if getattr(args, "post_dir", None) is not None:
         post_dir = Path(args.post_dir) / f"{args.src_lang}-{args.tgt_lang}"
         post_dir.mkdir(parents=True, exist_ok=True)
+    slack_dir = None
+    if getattr(args, "slack_dir", None) is not None:
+        slack_dir = Path(args.slack_dir) / f"{args.src_lang}-{args.tgt_lang}"
+        slack_dir.mkdir(parents=True, exist_ok=True)
     if not todo:
         if margin is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:   # the other ranks wait for this one in the exchange
             margin.finish(_lib.context())
@@ -499,6 +535,9 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
         for i, p in enumerate(chunk):
             o, cnt = int(offs[i]), int(info[i, 0])
             writes.append(out_pool.apply_async(_write_result, (p.output_path, align[o:o + cnt], scores[o:o + cnt])))
+            if slack_dir is not None:
+                writes.append(out_pool.apply_async(_write_slack, ((slack_dir / os.path.basename(p.output_path)).as_posix(), align[o:o + cnt],
+                                                                  scores[o:o + cnt], pb.h_slack.numpy()[o:o + cnt])))
             if post_dir is not None:
                 writes.append(out_pool.apply_async(_write_post, ((post_dir / os.path.basename(p.output_path)).as_posix(), align[o:o + cnt],
                                                                  scores[o:o + cnt], held[0][i][4], args.max_cost, chain)))
@@ -564,6 +603,10 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
                     contact = pb.band_contact(0, guard)
                     pb.h_contact = torch.empty(contact.shape, dtype=contact.dtype, pin_memory=True)
                     pb.h_contact.copy_(contact, non_blocking=True)   # (lands before the event of fetch_async)
+            if slack_dir is not None:   # one call behind run(); read back with the results
+                sl, _ = pb.row_slack()
+                pb.h_slack = torch.empty(sl.shape, dtype=sl.dtype, pin_memory=True)
+                pb.h_slack.copy_(sl, non_blocking=True)
             if rescore_tsv is not None and any(q[6] is not None and q[6][0] == "ok" for q in prepared):
                 # two calls behind run(): the returned paths' totals, then the given paths'; read back with the results
                 ok = [q[6] is not None and q[6][0] == "ok" for q in prepared]

@@ -83,6 +83,21 @@ def read_alignments_with_score(fin) -> List[Tuple[List[int], List[int], float]]:
     return out
 
 
+def read_alignments_with_slack(fin) -> List[Tuple[List[int], List[int], float, float]]:
+    """`[src ids]:[tgt ids]:score:slack` per line (seg_align.align --slack_dir) -> [(src, tgt, score, slack)]; the slack
+    may be `inf` (no other path in the band) or `nan`."""
+    out = []
+    with open(fin, 'rt', encoding="utf-8") as infile:
+        for line in infile:
+            f = _fields(line)
+            assert len(f) == 4, 'Got line "%s", which does not have four ":" separated fields' % line.strip()
+            try:
+                out.append((literal_eval(f[0]), literal_eval(f[1]), float(f[2]), float(f[3])))
+            except Exception:
+                raise Exception('Failed to parse line "%s"' % line.strip())
+    return out
+
+
 def write_alignment(alignments, path: Union[Path, str]) -> None:
     with open(path, mode="w") as fp:
         for src_segs, tgt_segs in alignments:

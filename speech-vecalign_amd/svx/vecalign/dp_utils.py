@@ -564,6 +564,29 @@ class PreparedBatch:
         ctx.check(ctx.lib.svx_score_alignments(ctx.h, cg, npairs))
         return GivenScores(scores, total, report, offs, [g is None for g in given], (h_rows, h_info, d_rows, d_info, self), cg)
 
+    def row_slack(self):
+        """svx_row_slack for the last run() on the context (include/svx.h): the slack of every returned row at level 0 --
+        the total of the best path of the same band that does NOT contain the row, minus the total of the returned path.
+        0: a second optimum exists (the row was picked by the tie rule); small: ambiguous; several deletion penalties:
+        solid.  Not clamped: float64 rounding may leave a tiny negative value.  -> (slack, summary): a float64 device
+        tensor laid out like self.scores (pair i at self.offs[i]; NaN past a pair's rows), and an int32 device tensor
+        [pairs, 4] = (rows, rows with slack == 0, rows with slack == +inf, 0), -1 in all four for a failed pair.
+        A run that took the tile sweep (band above 64 cells in the straight and around-wide modes) keeps no cost array and
+        raises SvxError.  Asynchronous on the current stream."""
+        ctx = self.ctx
+        t = ctx.torch
+        npairs = len(self.vecs)
+        ctx.use_current_stream()
+        slack = t.full((max(1, int(self.offs[-1])),), float("nan"), dtype=t.float64, device=ctx.tdev)
+        summary = t.zeros((npairs, 4), dtype=t.int32, device=ctx.tdev)
+        ptrs = (ctypes.c_void_p * max(1, npairs))()
+        for i in range(npairs):
+            ptrs[i] = slack.data_ptr() + 8 * int(self.offs[i])
+        ctx.check(ctx.lib.svx_row_slack(ctx.h, ptrs, _p(summary), npairs))
+        self.slack, self.slack_summary, self._slack_ptrs = slack, summary, ptrs   # alive as long as the batch
+        ctx.hold(self)
+        return slack, summary
+
     def run_widen(self, guard=0, max_width_over2=None, max_rounds=4):
         """run() followed by band doubling (svx_align_widen, include/svx.h): pairs whose path touches the band edge are
         searched again around that path in twice the band, up to `max_rounds` times and `max_width_over2` (default:
@@ -786,14 +809,16 @@ def align_batch(pairs, final_alignment_types, del_percentile_frac, width_over2, 
 
 def vecalign(vecs0, vecs1, final_alignment_types, del_percentile_frac, width_over2, max_size_full_dp,
              costs_sample_size, num_samps_for_norm, norms0=None, norms1=None, normalize_inputs_inplace=False,
-             full_stack=False, given=None, search="coarse_to_fine"):
+             full_stack=False, given=None, search="coarse_to_fine", return_slack=False):
     """dp_utils.py:381-537.  Returns {0: {'final_alignments', 'alignment_scores', 'del_penalty',
     'size0', 'size1', 'alignment_types'}, d: {'del_penalty', 'size0', 'size1'} ...}; with full_stack=True every
     depth also carries the intermediates the reference keeps (n0, n1, searchpath, a_b_costs, b_offset, a_b_csum,
     a_b_xp, a_b_yp, new_b_offset, alignments: PreparedBatch.level_stack), copied back from the device.
     given: alignments [(x ids, y ids)] (or int rows [r, 4]) to price with this call's costs (svx_score_alignments); then
     stack[0]['given'] = dict(verdict, found_total, given_total, del_penalty, report, scores) (search_error()).
-    search: "coarse_to_fine" (the reference) or "straight" (PreparedBatch: depth 0 only)."""
+    search: "coarse_to_fine" (the reference) or "straight" (PreparedBatch: depth 0 only).
+    return_slack: stack[0]['row_slack'] = float64 array, the slack of every final alignment (PreparedBatch.row_slack), and
+    stack[0]['slack_summary'] = (rows, rows with slack 0, rows with slack +inf, 0)."""
     if search != "coarse_to_fine":
         max_size_full_dp = 1 << 30
     pb = PreparedBatch([(vecs0, vecs1)], final_alignment_types, del_percentile_frac, width_over2, max_size_full_dp,
@@ -824,6 +849,10 @@ def vecalign(vecs0, vecs1, final_alignment_types, del_percentile_frac, width_ove
         stack[0]['given'] = dict(verdict=search_error(own['total'], got['total'], got['report']), found_total=own['total'],
                                  given_total=got['total'], del_penalty=got['del_penalty'], report=got['report'],
                                  scores=got['scores'])
+    if return_slack:
+        sl, summ = pb.row_slack()
+        stack[0]['row_slack'] = sl.cpu().numpy()[:len(alignments)].copy()
+        stack[0]['slack_summary'] = tuple(int(v) for v in summ.cpu().numpy()[0])
     if normalize_inputs_inplace:
         make_norm1(vecs0)
         make_norm1(vecs1)
@@ -972,6 +1001,51 @@ def sparse_traceback(a_b_csum, a_b_xp, a_b_yp, b_offset, xsize, ysize):
     if n < 0:
         raise Exception('traceback bug')
     return rows_to_alignments(rows.cpu().numpy()[:n]), scores.cpu().numpy()[:n].copy()
+
+
+def sparse_dp_backward(a_b_costs, b_offset_in, alignment_types, del_penalty, x_in_size, y_in_size):
+    """svx_sparse_dp_backward (include/svx.h): the backward band DP over the edges sparse_dp relaxes -> Bk [A+2][B]
+    float64, the cheapest way from every band cell to the end node (+inf where there is none)."""
+    from .dp_core import _typed, _types
+    ctx = _ctx()
+    t = ctx.torch
+    a_b_costs = _typed(a_b_costs, np.float32, 3, "a_b_costs")
+    b_offset_in = _typed(b_offset_in, np.int32, 1, "b_offset_in")
+    types, T = _types(alignment_types)
+    Tc, A, B = a_b_costs.shape
+    assert Tc == T
+    bsum = t.empty((A + 2, B), dtype=t.float64, device=ctx.tdev)
+    c = _dev(ctx, a_b_costs) if a_b_costs.size else t.empty(1, dtype=t.float32, device=ctx.tdev)
+    bin_ = _dev(ctx, b_offset_in)
+    ctx.check(ctx.lib.svx_sparse_dp_backward(ctx.h, _p(c), _p(bin_), A, B, types, T, float(del_penalty), int(x_in_size),
+                                             int(y_in_size), _p(bsum)))
+    return bsum.cpu().numpy()
+
+
+def path_slack(a_b_costs, b_offset_in, alignment_types, del_penalty, x_in_size, y_in_size, a_b_csum, a_b_bsum, rows):
+    """svx_path_slack (include/svx.h): the slack of int rows [n, 4] = (x_start, x_len, y_start, y_len) on the planes
+    a_b_csum (sparse_dp) and a_b_bsum (sparse_dp_backward) -> float64 [n]; NaN for a row that is no edge of the band."""
+    from .dp_core import _typed, _types
+    ctx = _ctx()
+    t = ctx.torch
+    a_b_costs = _typed(a_b_costs, np.float32, 3, "a_b_costs")
+    b_offset_in = _typed(b_offset_in, np.int32, 1, "b_offset_in")
+    types, T = _types(alignment_types)
+    Tc, A, B = a_b_costs.shape
+    assert Tc == T
+    rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 4)
+    n = len(rows)
+    csum = _dev(ctx, np.ascontiguousarray(a_b_csum, dtype=np.float64))
+    bsum = _dev(ctx, np.ascontiguousarray(a_b_bsum, dtype=np.float64))
+    assert tuple(csum.shape) == (A + 2, B) and tuple(bsum.shape) == (A + 2, B)
+    c = _dev(ctx, a_b_costs) if a_b_costs.size else t.empty(1, dtype=t.float32, device=ctx.tdev)
+    bin_ = _dev(ctx, b_offset_in)
+    drows = _dev(ctx, rows if n else np.zeros((1, 4), np.int32))
+    cnt = t.tensor([n], dtype=t.int32).to(ctx.tdev)
+    out = t.full((max(1, n),), float("nan"), dtype=t.float64, device=ctx.tdev)
+    ctx.check(ctx.lib.svx_path_slack(ctx.h, _p(c), _p(bin_), A, B, types, T, float(del_penalty), int(x_in_size), int(y_in_size),
+                                     _p(csum), _p(bsum), _p(drows), _p(cnt), n, _p(out)))
+    return out.cpu().numpy()[:n].copy()
 
 
 def make_search_path(alignments, size0=0, size1=0, upsample=False):
