@@ -691,6 +691,89 @@ int svx_path_slack(svx_ctx *ctx, const float *costs, const int32_t *b_offset_in,
 int svx_row_slack(svx_ctx *ctx, double *const *slack /* HOST [n_pairs] of device [n+m+2] */,
                   int32_t *summary /* device [n_pairs][4], 16-byte aligned */, int n_pairs);
 
+/* ---- row alternatives: what would the DP have done instead? (csrc/svx_alt.hip) ----------------------
+ * Slack says how decided a row is.  These entries name the competitor: the edge that wins the row's cut when the row is
+ * forbidden, and the rows of the best path through that edge that replace returned rows (its detour).  For rows the
+ * caller believes in they give the regret: how much dearer the best path containing the row is than the returned one.
+ * Notation, cells, kinds, the edge sets E and E_b, F, Bk, total and the move list are those of the slack section above.
+ * The definitions apply to the rows 0 .. R-1 of one pair, which form a path: their nodes are P_0, P_1, .., P_R, P_i the
+ * start of row i and P_R the end of row R-1 (for the DP's own rows P_0 = (0,0) and P_R = (xs, ys)).  A node that is no
+ * lattice node or no band cell is not a P_i; when rows that are no path put several nodes on one diagonal, one of them
+ * counts, unspecified which (nothing out of range is read or written either way).
+ * A row IS AN EDGE under the rule of svx_path_slack: 0 <= x_start, x_len, y_start, y_len; x_start + x_len <= xs;
+ *   y_start + y_len <= ys; x_len + y_len >= 1; its end diagonal is below A+2; (x_len, y_len) is a move of the list (its
+ *   move index t is the first such entry); both of its nodes are band cells.  No address is formed before that is known.
+ *
+ * Alternative edge of row r with cut c = x_start + y_start.  The candidates are the crossing edges e = u -> v by move t,
+ *   e != e* (an edge from u* by the row's move is e*, whichever list entry it uses), cand(e) = (F(u) + w) + Bk(v) exactly
+ *   as in the slack definition.
+ *     alt[r] = min cand, slack[r] = alt[r] - total (the bits svx_path_slack / svx_row_slack write).
+ *   The alternative edge is the candidate with cand == alt[r] that comes first by diagonal of v ascending, then cell b of
+ *   v ascending, then move index t ascending.  There is none when alt[r] = +inf or the row is no edge.
+ *     edge[r] = (x_u, xo, y_u, yo), or (-1, -1, -1, -1) without one.
+ * Detour of row r: computed when r has an alternative edge, `detour` is not NULL and slack[r] <= max_slack (a plain double
+ *   comparison: NaN fails it, +inf measures every row).  With K = max_detour, nb and nf the rows taken so far:
+ *   Backward part.  Start from u.  While the node is none of the P_i: when nb == K - 1 the status is 1; else take the
+ *     stored back-pointer (xp, yp) of the node's cell -- the step svx_sparse_traceback takes, under its conditions: xp, yp
+ *     >= 0, xp + yp >= 1, xp <= x, yp <= y; the step must also be a move of the list and the predecessor a band cell, or
+ *     the status is 3 -- and prepend the row (x - xp, xp, y - yp, yp).  The walk stops at L = P_lo.
+ *   Forward part.  Start from v.  While the node is none of the P_i: when nb + 1 + nf == K the status is 1; else take the
+ *     first move t in list order whose edge node -> s is in E or E_b and for which w + Bk(s) == Bk(node) holds as doubles
+ *     (one exists whenever Bk(node) is finite; otherwise the status is 3), and append the row.  The walk stops at J = P_hi.
+ *   The detour is the backward rows in document order, the alternative edge, the forward rows: n_detour <= K rows that
+ *   replace the returned rows lo .. hi-1; on a path lo <= r < hi.  detour[r][j] = row j; detour_scores[r][j] = 0.0 for a
+ *   deletion and max((double) cost cell, 0) / (double) (xo yo) for a typed row (the cost cell of the move index taken: the
+ *   edge's t, the forward walk's t, the first list entry of a back-pointer step), as process_scores (dp_utils.py:89-102)
+ *   scores a row from its own cost.
+ *     span[r] = (lo, hi, n_detour, status): status 0 detour written; 1 too long (the detour has more than K rows);
+ *     2 not measured (no alternative edge, no `detour`, or slack above max_slack); 3 walk failed.  For every status but 0
+ *     span[r] = (-1, -1, -1, status) and the detour slots of the row are left untouched, as are slots j >= n_detour.
+ * Regret of a given row g (any four integers): NaN when g is no edge (no address is formed), else
+ *     regret = ((F(u) + w) + Bk(v)) - total, w the weight of the row's move index,
+ *   +inf when u is unreachable or v cannot reach the end, 0 for a returned row up to the rounding bound stated for slack.
+ *   max_slack does not apply.  Rows g < given_info[0] (clamped to [0, given_cap]) are written, nothing past them; with
+ *   given_info[1] != 0 nothing is written.
+ *
+ * svx_path_alternatives: the kernels of svx_row_alternatives on caller-supplied planes, any B: the arguments of
+ *   svx_path_slack, then xp, yp [A+2][B] (svx_sparse_dp), then one svx_alt record (its slack, detour, detour_scores and
+ *   given may be NULL; edge, span [cap][4]; detour [cap][K][4]; detour_scores [cap][K]).  Rows r < n_rows (clamped to [0,
+ *   cap]) are written.  SVX_ERR_ARG with text, nothing queued: the cases of svx_path_slack; null xp / yp / alt / edge /
+ *   span; edge, span, detour or given not 16-byte aligned; max_detour outside [1, SVX_ALT_MAX_DETOUR]; a NaN max_slack;
+ *   regret or given_info NULL, or a negative given_cap, beside a non-NULL given.  The node table (8 bytes x (A+2)) is the
+ *   context's post-processing scratch.
+ * svx_row_alternatives follows every rule of svx_row_slack: level 0 of the LAST svx_align_batch / svx_align_around call,
+ *   both halves of a pipelined call, in the pair order of svx_debug_level; n_pairs must equal that call's pair count;
+ *   svx_flush first; asynchronous on the context's stream, no host synchronisation.  It reads what svx_row_slack reads and
+ *   the level's back-pointers in either layout (a_b_bp bytes, or the a_b_xp / a_b_yp planes).  alt (HOST [n_pairs]): the
+ *   arrays of pair p hold n + m + 2 rows; alt[p].edge == NULL skips the pair: nothing of it is written.
+ *   summary (device [n_pairs][4] int32, 16-byte aligned) = (rows, rows with an alternative edge, detours written, detours
+ *   too long); a pair with info[1] != 0 gets (-1, -1, -1, -1) and nothing else of it is written.
+ *   SVX_ERR_ARG with text, nothing queued: a call that ran the tile sweep, which keeps no cost array; no earlier successful
+ *   call; a pair count that differs; a null alt / summary; a misaligned summary; and per pair that is not skipped the
+ *   record rules above.
+ *   Launches: the backward sweep of svx_row_slack (the same kernels, so slack is the same bits), k_row_alt with one
+ *   workgroup per pair and one wave per row, and k_given_regret with one thread per given row when any pair has given rows.
+ *   Scratch: the descriptors and per pair one Bk plane of (path capacity + 2) x B doubles and a node table of 8 bytes x
+ *   (path capacity + 2), in the context's post-processing scratch (svx_scratch_bytes). */
+#define SVX_ALT_MAX_DETOUR 256
+typedef struct svx_alt {
+    double  *slack;            /* device [n+m+2], nullable: alt - total, the bits svx_row_slack writes */
+    int32_t *edge;             /* device [n+m+2][4], 16-byte aligned */
+    int32_t *span;             /* device [n+m+2][4], 16-byte aligned */
+    int32_t *detour;           /* device [n+m+2][K][4], nullable: edges only, every span = (-1,-1,-1,2) */
+    double  *detour_scores;    /* device [n+m+2][K], nullable */
+    const int32_t *given;      /* device [given_cap][4], nullable, 16-byte aligned */
+    const int32_t *given_info; /* device [2] as svx_given.info */
+    int32_t given_cap, pad;
+    double  *regret;           /* device [given_cap] */
+} svx_alt;
+int svx_row_alternatives(svx_ctx *ctx, const svx_alt *alt /* HOST [n_pairs] */, int max_detour, double max_slack,
+                         int32_t *summary /* device [n_pairs][4] */, int n_pairs);
+int svx_path_alternatives(svx_ctx *ctx, const float *costs, const int32_t *b_offset_in, int A, int B, const int32_t *types_host,
+                          int T, double del_penalty, int x_in_size, int y_in_size, const double *csum, const double *bsum,
+                          const int32_t *xp, const int32_t *yp, const int32_t *rows /* [n_rows][4] */,
+                          const int32_t *n_rows /* device [1] */, int cap, const svx_alt *one, int max_detour, double max_slack);
+
 /* Per-level intermediates of the LAST svx_align_batch call on this context -- the entries of the `stack` the reference
  * returns (dp_utils.py:412-537) -- as device pointers into the context's scratch arena (valid until the next call;
  * the scalar fields are read back, which synchronises the stream).  Pointers are NULL for what a level does not have

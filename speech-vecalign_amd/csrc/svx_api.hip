@@ -483,6 +483,22 @@ int svx_path_slack(svx_ctx* ctx, const float* costs, const int32_t* b_offset_in,
     return svxl_path_slack(ctx, costs, b_offset_in, A, B, ty, del_penalty, x_in_size, y_in_size, csum, bsum, rows, n_rows, cap, slack);
 }
 
+int svx_path_alternatives(svx_ctx* ctx, const float* costs, const int32_t* b_offset_in, int A, int B, const int32_t* types_host, int T,
+                          double del_penalty, int x_in_size, int y_in_size, const double* csum, const double* bsum, const int32_t* xp,
+                          const int32_t* yp, const int32_t* rows, const int32_t* n_rows, int cap, const svx_alt* one, int max_detour,
+                          double max_slack) {
+    NEED(ctx, ctx && b_offset_in && csum && bsum && xp && yp && n_rows && one && (costs || T == 0), "svx_path_alternatives: null argument");
+    NEED(ctx, cap >= 0 && (rows || cap == 0), "svx_path_alternatives: cap %d with null rows", cap);
+    NEED(ctx, aligned16(rows), "svx_path_alternatives: rows must be 16-byte aligned");
+    NEED(ctx, A >= 1 && B >= 1, "svx_path_alternatives: empty cost band");
+    NEED(ctx, x_in_size >= 0 && y_in_size >= 0, "svx_path_alternatives: negative document size");
+    SvxTypes ty;
+    int rc = make_types(ctx, types_host, T, &ty);
+    if (rc) return rc;
+    return svxl_path_alternatives(ctx, costs, b_offset_in, A, B, ty, del_penalty, x_in_size, y_in_size, csum, bsum, xp, yp, rows, n_rows, cap,
+                                  one, max_detour, max_slack);
+}
+
 int svx_make_norm1(svx_ctx* ctx, float* vecs, int64_t rows, int d) {
     NEED(ctx, ctx && (vecs || rows == 0), "svx_make_norm1: null argument");
     int rc = check_dim(ctx, d);

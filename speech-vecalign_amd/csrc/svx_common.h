@@ -256,7 +256,8 @@ struct svx_ctx {
     // offsets, compacted rows), svx_knn_search_groups (svx_groupsearch.hip: offsets, workgroup table) and svx_time_prior
     // (svx_prior.hip: descriptors, prefix counts), svx_band_contact and svx_align_widen (svx_contact.hip: descriptors, the
     // report rows, the staged priors of a round), svx_score_alignments (svx_given.hip: descriptors, chunk table, partial sums)
-    // and svx_row_slack (svx_slack.hip: descriptors, one backward plane per pair).  They go through svxl_scratch_begin /
+    // svx_row_slack (svx_slack.hip: descriptors, one backward plane per pair) and svx_row_alternatives / svx_path_alternatives
+    // (svx_alt.hip: descriptors, per pair one backward plane and one node table).  They go through svxl_scratch_begin /
     // svxl_scratch_upload only.
     char* post_buf;
     size_t post_bytes;        // counted in svx_scratch_bytes
@@ -342,8 +343,30 @@ int svxl_prior_ingest_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs);
 bool svxl_last_batch(svx_ctx*, const SvxPairDev** host, int* n_pairs, int* band);
 // storage type, embedding dimension and level-0 type set of that same call (svx_given.hip); false when there is none
 bool svxl_last_batch_types(svx_ctx*, int* dtype, int* d, const SvxTypes** types);
-// row slack (svx_slack.hip): the backward band DP and the slack of the rows of a path, per-op
+// row slack (svx_slack.hip): the per-pair descriptor of its kernels, the backward band DP and the slack of the rows of a
+// path, per-op
+struct SlackPair {
+    const float* costs;
+    const int* boff_in;     // [A]
+    const int* path_len;    // device A (the pipeline), or null: A below
+    const double* pen_dev;  // device penalty (the pipeline), or null: pen below
+    const int* status;      // the aligner's info[1] of the pair, or null
+    const double* csum;     // [A+2][B] forward plane (k_path_slack only)
+    double* bsum;           // [A+2][B] backward plane; null: the pair is skipped
+    const int* rows;        // [cap][4]
+    const int* n_rows;      // [1]
+    double* slack;          // [cap]
+    int* summary;           // [4] or null (per-op entry)
+    double pen;
+    int A, xs, ys, cap;
+};
 int svxl_sparse_dp_backward(svx_ctx*, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen,
                             int xs, int ys, double* bsum);
 int svxl_path_slack(svx_ctx*, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen, int xs,
                     int ys, const double* csum, const double* bsum, const int* rows, const int* n_rows, int cap, double* slack);
+// the backward sweep of n pairs over device descriptors (a pair with bsum == null is skipped); atb: costs are [A][T][B]
+int svxl_backward_batch(svx_ctx*, const SlackPair* dev, int n, const SvxTypes& types, int B, int atb);
+// row alternatives (svx_alt.hip), per-op: the arguments are checked there
+int svxl_path_alternatives(svx_ctx*, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen, int xs,
+                           int ys, const double* csum, const double* bsum, const int* xp, const int* yp, const int* rows, const int* n_rows,
+                           int cap, const svx_alt* alt, int max_detour, double max_slack);

@@ -28,22 +28,6 @@
 
 namespace {
 
-struct SlackPair {
-    const float* costs;
-    const int* boff_in;     // [A]
-    const int* path_len;    // device A (the pipeline), or null: A below
-    const double* pen_dev;  // device penalty (the pipeline), or null: pen below
-    const int* status;      // the aligner's info[1] of the pair, or null
-    const double* csum;     // [A+2][B] forward plane (k_path_slack only)
-    double* bsum;           // [A+2][B] backward plane; null: the pair is skipped
-    const int* rows;        // [cap][4]
-    const int* n_rows;      // [1]
-    double* slack;          // [cap]
-    int* summary;           // [4] or null (per-op entry)
-    double pen;
-    int A, xs, ys, cap;
-};
-
 struct BkArgs {
     const float* costs;
     const int* boff_in;
@@ -507,6 +491,10 @@ int svxl_path_slack(svx_ctx* ctx, const float* costs, const int* boff_in, int A,
     hipLaunchKernelGGL(k_path_slack, dim3(1), dim3(SK_THREADS), 0, ctx->stream, (const SlackPair*)nullptr, one, 1, types, B, 0);
     SVX_LAUNCH_CHECK(ctx, "k_path_slack");
     return SVX_OK;
+}
+
+int svxl_backward_batch(svx_ctx* ctx, const SlackPair* dev, int n, const SvxTypes& types, int B, int atb) {
+    return launch_backward(ctx, dev, SlackPair{}, n, types, B, atb);
 }
 
 extern "C" int svx_row_slack(svx_ctx* ctx, double* const* slack, int32_t* summary, int n_pairs) {

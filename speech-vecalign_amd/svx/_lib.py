@@ -88,6 +88,15 @@ class Given(ctypes.Structure):
                 ("scores", c_vp), ("total", c_vp), ("report", c_vp)]
 
 
+class Alt(ctypes.Structure):
+    """svx_alt: where the alternatives of one pair go (svx_row_alternatives, svx_path_alternatives)."""
+    _fields_ = [("slack", c_vp), ("edge", c_vp), ("span", c_vp), ("detour", c_vp), ("detour_scores", c_vp),
+                ("given", c_vp), ("given_info", c_vp), ("given_cap", ctypes.c_int32), ("pad", ctypes.c_int32), ("regret", c_vp)]
+
+
+SVX_ALT_MAX_DETOUR = 256
+
+
 class ConcatParams(ctypes.Structure):
     """svx_concat_params (include/svx.h)."""
     _fields_ = [
@@ -158,6 +167,9 @@ _SIGS = {
                                 ctypes.POINTER(WidenParams), c_vp]),
     "svx_score_alignments": (c_int, [c_vp, ctypes.POINTER(Given), c_int]),
     "svx_row_slack": (c_int, [c_vp, ctypes.POINTER(c_vp), c_vp, c_int]),
+    "svx_row_alternatives": (c_int, [c_vp, ctypes.POINTER(Alt), c_int, c_f64, c_vp, c_int]),
+    "svx_path_alternatives": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_f64, c_int, c_int,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(Alt), c_int, c_f64]),
     "svx_alignment_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), c_int, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "svx_concat_rows": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(Pair), ctypes.POINTER(Frames), c_int, ctypes.POINTER(ConcatParams), c_i64,
                                 c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),

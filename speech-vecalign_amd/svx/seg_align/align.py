@@ -42,6 +42,16 @@ own alignment lines with a fourth field, the row's slack (svx_row_slack) -- the 
 does not contain the row, minus the total of the returned path: `[0, 1]:[0]:0.349737:0.012345`.  0 means a second optimum
 exists and the tie rule picked the row; a small value means the row is ambiguous (a repeated phrase, near-silent segments);
 several deletion penalties mean it is solid; `inf` means no other path exists in the band.  The alignment files do not change.
+
+--alt_dir DIR names the competitor behind a small slack (svx_row_alternatives): DIR/{src}-{tgt}/{s}-{t}.txt holds one
+tab-separated line per returned row that has a written detour -- row number, slack, lo, hi, then the detour's rows in the
+alignment files' syntax: the rows of the best path avoiding the row that replace the returned rows lo .. hi-1.  Rows with a
+slack above --alt_max_slack (default inf) are not measured and detours of more than --alt_max_detour rows (default 16, at most
+256; a guess until detour lengths on real documents are known) are not written.  --regret_dir DIR goes with --rescore_dir:
+DIR/{src}-{tgt}/{s}-{t}.txt holds the rows of the given path (gaps filled with deletions, as it is priced) as
+`[src ids]:[tgt ids]:regret`, the total of the best path of the band containing the row minus the returned total: 0 for a row
+the DP returned or could have, small for a near miss, large for a row the model rejects, `nan` for a row the band or the type
+set does not hold.  The alignment files do not change.
 """
 import argparse
 import dataclasses
@@ -127,6 +137,19 @@ def parse_args(argv=None):
                         "(svx_row_slack): best total of a path of the same band without the row minus the returned path's total, "
                         "%%.6f; 0 = tied with another optimum, inf = no other path.  Needs the band's cost array: not for bands above "
                         "64 cells in --mode band / dense / --prior_band (the tile sweep keeps none)")
+    p.add_argument("--alt_dir", type=str, default=None,
+                   help="also write {alt_dir}/{src}-{tgt}/{s}-{t}.txt: per returned row with a written detour one tab-separated line "
+                        "'row slack lo hi detour rows...' (svx_row_alternatives): the rows of the best path of the same band without "
+                        "the row that replace the returned rows lo .. hi-1, in the alignment files' syntax.  Needs the band's cost "
+                        "array, like --slack_dir")
+    p.add_argument("--alt_max_detour", type=int, default=16,
+                   help="--alt_dir: longest detour written, in rows (1 .. 256); the default is a guess until detour lengths on real "
+                        "documents are known")
+    p.add_argument("--alt_max_slack", type=float, default=float("inf"), help="--alt_dir: measure only rows with at most this slack")
+    p.add_argument("--regret_dir", type=str, default=None,
+                   help="--rescore_dir: also write {regret_dir}/{src}-{tgt}/{s}-{t}.txt: the given path's rows as src_ids:tgt_ids:regret, "
+                        "the best total of a path of the band WITH the row minus the returned path's total (svx_row_alternatives); "
+                        "nan = the band or the type set does not hold the row")
     p.add_argument("--batch_size", type=int, default=32, help="document pairs per device pass")
     p.add_argument("--io_threads", type=int, default=None, help="host threads that parse / read ahead of the GPU (default: the CPU count, at most 32)")
     p.add_argument("--seed", type=int, default=None, help="derive one sampling stream per pair from (seed, pair index)")
@@ -184,6 +207,24 @@ def parse_args(argv=None):
         cells = 2 * max(3, (args.band + 1) // 2) if args.mode == "band" else (args.prior_band if args.mode == "around" else None)
         if cells is not None and cells > 64:   # (--mode dense: the band follows the documents; the library refuses it)
             p.error(f"--slack_dir needs the band's cost array: a band of {cells} cells runs the tile sweep, which keeps no cost "
+                    "array (at most 64 cells in --mode band and with --prior_band)")
+    if args.regret_dir is not None and args.rescore_dir is None:
+        p.error("--regret_dir needs --rescore_dir: the rows whose regret is wanted come from its files")
+    if not 1 <= args.alt_max_detour <= 256:
+        p.error("--alt_max_detour must be 1 .. 256")
+    if args.alt_max_slack != args.alt_max_slack:
+        p.error("--alt_max_slack must be a number")
+    for flag in ("alt_dir", "regret_dir"):
+        if getattr(args, flag) is None:
+            continue
+        if args.widen:
+            p.error(f"--{flag} cannot be combined with --widen: after band doubling the last device call holds only the pairs "
+                    "that were searched again")
+        if args.skip_existing:
+            p.error(f"--{flag} cannot be combined with --skip_existing: a skipped pair has no costs to measure alternatives with")
+        cells = 2 * max(3, (args.band + 1) // 2) if args.mode == "band" else (args.prior_band if args.mode == "around" else None)
+        if cells is not None and cells > 64:   # (--mode dense: the band follows the documents; the library refuses it)
+            p.error(f"--{flag} needs the band's cost array: a band of {cells} cells runs the tile sweep, which keeps no cost "
                     "array (at most 64 cells in --mode band and with --prior_band)")
     if args.concat_max_num is not None and not 1 <= args.concat_max_num <= 8:
         p.error("--concat_max_num must be 1 .. 8")
@@ -317,6 +358,34 @@ def format_slack_lines(rows: np.ndarray, scores: np.ndarray, slack: np.ndarray) 
 
 def _write_slack(path: str, rows: np.ndarray, scores: np.ndarray, slack: np.ndarray):
     _write_text(path, format_slack_lines(rows, scores, slack))
+
+
+def format_alt_lines(slack: np.ndarray, span: np.ndarray, detours) -> str:
+    """--alt_dir: one line per row r with a written detour (span[r] = (lo, hi, n_detour, 0)): r, '%.6f' of the slack, lo, hi and
+    the detour's rows as the alignment file prints rows, tab-separated.  detours[r]: None or (rows [k, 4], scores [k])."""
+    out = []
+    for r in range(len(span)):
+        if int(span[r][3]) != 0 or detours[r] is None:
+            continue
+        rows = format_alignment_rows(detours[r][0], detours[r][1]).decode().splitlines()
+        out.append("\t".join(["%d" % r, "%.6f" % float(slack[r]), "%d" % int(span[r][0]), "%d" % int(span[r][1])] + rows) + "\n")
+    return "".join(out)
+
+
+def format_regret_lines(rows: np.ndarray, regret: np.ndarray) -> str:
+    """--regret_dir: `[src ids]:[tgt ids]:%.6f` per given row, the field being the row's regret ('nan': no edge of the band)."""
+    lines = format_alignment_rows(rows, None).decode().splitlines()
+    assert len(lines) == len(regret), f"{len(lines)}, {len(regret)}"
+    return "".join("%s:%.6f\n" % (ln, float(v)) for ln, v in zip(lines, regret))
+
+
+def _write_alt(path: str, slack: np.ndarray, span: np.ndarray, detour: np.ndarray, scores: np.ndarray):
+    detours = [(detour[r, :span[r, 2]], scores[r, :span[r, 2]]) if span[r, 3] == 0 else None for r in range(len(span))]
+    _write_text(path, format_alt_lines(slack, span, detours))
+
+
+def _write_regret(path: str, rows: np.ndarray, regret: np.ndarray):
+    _write_text(path, format_regret_lines(rows, regret))
 
 
 def _write_post(path: str, rows: np.ndarray, scores: np.ndarray, frames, max_cost, chain: dict):
@@ -471,6 +540,11 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
     if getattr(args, "slack_dir", None) is not None:
         slack_dir = Path(args.slack_dir) / f"{args.src_lang}-{args.tgt_lang}"
         slack_dir.mkdir(parents=True, exist_ok=True)
+    alt_dir, regret_dir = (None if getattr(args, flag, None) is None else Path(getattr(args, flag)) / f"{args.src_lang}-{args.tgt_lang}"
+                           for flag in ("alt_dir", "regret_dir"))
+    for dpath in (alt_dir, regret_dir):
+        if dpath is not None:
+            dpath.mkdir(parents=True, exist_ok=True)
     if not todo:
         if margin is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:   # the other ranks wait for this one in the exchange
             margin.finish(_lib.context())
@@ -538,6 +612,15 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
             if slack_dir is not None:
                 writes.append(out_pool.apply_async(_write_slack, ((slack_dir / os.path.basename(p.output_path)).as_posix(), align[o:o + cnt],
                                                                   scores[o:o + cnt], pb.h_slack.numpy()[o:o + cnt])))
+            if alt_dir is not None:
+                h = pb.h_alt
+                writes.append(out_pool.apply_async(_write_alt, ((alt_dir / os.path.basename(p.output_path)).as_posix(),
+                                                                h['slack'].numpy()[o:o + cnt], h['span'].numpy()[o:o + cnt],
+                                                                h['detour'].numpy()[o:o + cnt], h['detour_scores'].numpy()[o:o + cnt])))
+            if regret_dir is not None and pb.regret_rows[i] is not None:
+                g0, g1 = int(pb.alt_given_offs[i]), int(pb.alt_given_offs[i + 1])
+                writes.append(out_pool.apply_async(_write_regret, ((regret_dir / os.path.basename(p.output_path)).as_posix(),
+                                                                   pb.regret_rows[i], pb.h_alt['regret'].numpy()[g0:g1])))
             if post_dir is not None:
                 writes.append(out_pool.apply_async(_write_post, ((post_dir / os.path.basename(p.output_path)).as_posix(), align[o:o + cnt],
                                                                  scores[o:o + cnt], held[0][i][4], args.max_cost, chain)))
@@ -607,6 +690,16 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
                 sl, _ = pb.row_slack()
                 pb.h_slack = torch.empty(sl.shape, dtype=sl.dtype, pin_memory=True)
                 pb.h_slack.copy_(sl, non_blocking=True)
+            if alt_dir is not None or regret_dir is not None:   # one call behind run(); read back with the results
+                from ..vecalign.dp_utils import given_rows_from_alignments
+                pb.regret_rows = [given_rows_from_alignments(q[6][1]) if regret_dir is not None and q[6] is not None and q[6][0] == "ok"
+                                  else None for q in prepared]
+                alt = pb.row_alternatives(args.alt_max_detour, args.alt_max_slack, given=pb.regret_rows if regret_dir is not None else None,
+                                          detour=alt_dir is not None)
+                pb.alt_given_offs = alt.get('given_offs')
+                pb.h_alt = {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True) for k, v in alt.items() if torch.is_tensor(v)}
+                for k, hx in pb.h_alt.items():
+                    hx.copy_(alt[k], non_blocking=True)
             if rescore_tsv is not None and any(q[6] is not None and q[6][0] == "ok" for q in prepared):
                 # two calls behind run(): the returned paths' totals, then the given paths'; read back with the results
                 ok = [q[6] is not None and q[6][0] == "ok" for q in prepared]

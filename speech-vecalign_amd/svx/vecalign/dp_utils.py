@@ -587,6 +587,65 @@ class PreparedBatch:
         ctx.hold(self)
         return slack, summary
 
+    def row_alternatives(self, max_detour=16, max_slack=float("inf"), given=None, detour=True, skip=()):
+        """svx_row_alternatives for the last run() on the context (include/svx.h): per returned row at level 0 the edge that
+        wins the row's cut when the row is forbidden, and -- for rows with slack <= max_slack -- the detour, the at most
+        `max_detour` rows of the best path through that edge which replace returned rows lo .. hi-1.
+        given: None, or one entry per pair -- None, or int rows [g, 4] = (x_start, x_len, y_start, y_len) -- whose regret is
+        wanted: the total of the best path containing the row minus the returned total (NaN: no edge of the band).
+        detour=False: edges and slack only.  skip: indices of pairs to leave out (nothing of them is written).  -> dict of device tensors laid out like self.scores (pair i at self.offs[i]):
+        slack [rows] float64 (the bits of row_slack()), edge [rows, 4] int32 (x_u, xo, y_u, yo; -1 without one), span
+        [rows, 4] int32 (lo, hi, n_detour, status: 0 written, 1 too long, 2 not measured, 3 walk failed), detour [rows,
+        max_detour, 4] int32 and detour_scores [rows, max_detour] float64 (-1 / NaN where nothing is written), summary
+        [pairs, 4] int32 = (rows, rows with an edge, detours written, detours too long; -1 x 4 for a failed pair); with given
+        also regret [given rows] float64 and given_offs (numpy: pair i's given rows start at given_offs[i]).  A run that took
+        the tile sweep keeps no cost array and raises SvxError.  Asynchronous on the current stream."""
+        ctx = self.ctx
+        t = ctx.torch
+        npairs = len(self.vecs)
+        if given is not None and len(given) != npairs:
+            raise ValueError("row_alternatives: one `given` entry per document pair (%d given, %d pairs)" % (len(given), npairs))
+        ctx.use_current_stream()
+        K = int(max_detour)
+        n = max(1, int(self.offs[-1]))
+        out = dict(slack=t.full((n,), float("nan"), dtype=t.float64, device=ctx.tdev),
+                   edge=t.full((n, 4), -1, dtype=t.int32, device=ctx.tdev),
+                   span=t.full((n, 4), -1, dtype=t.int32, device=ctx.tdev),
+                   summary=t.zeros((npairs, 4), dtype=t.int32, device=ctx.tdev))
+        if detour:
+            out['detour'] = t.full((n, max(1, K), 4), -1, dtype=t.int32, device=ctx.tdev)
+            out['detour_scores'] = t.full((n, max(1, K)), float("nan"), dtype=t.float64, device=ctx.tdev)
+        keep = []
+        if given is not None:
+            host = [None if g is None else np.ascontiguousarray(np.asarray(g).reshape(-1, 4), dtype=np.int32) for g in given]
+            goffs = np.concatenate([[0], np.cumsum([0 if h is None else len(h) for h in host])]).astype(np.int64)
+            h_rows = t.zeros((max(1, int(goffs[-1])), 4), dtype=t.int32, pin_memory=True)
+            h_info = t.zeros((npairs, 2), dtype=t.int32, pin_memory=True)
+            for i, h in enumerate(host):
+                if h is not None:
+                    h_rows.numpy()[goffs[i]:goffs[i + 1]] = h
+                    h_info.numpy()[i, 0] = len(h)
+            d_rows, d_info = h_rows.to(ctx.tdev, non_blocking=True), h_info.to(ctx.tdev, non_blocking=True)
+            out['regret'] = t.full((max(1, int(goffs[-1])),), float("nan"), dtype=t.float64, device=ctx.tdev)
+            out['given_offs'] = goffs
+            keep = [h_rows, h_info, d_rows, d_info]
+        ca = (_lib.Alt * max(1, npairs))()
+        for i in range(npairs):
+            if i in skip:
+                continue
+            o, c = int(self.offs[i]), ca[i]
+            c.slack, c.edge, c.span = out['slack'].data_ptr() + 8 * o, out['edge'].data_ptr() + 16 * o, out['span'].data_ptr() + 16 * o
+            if detour:
+                c.detour = out['detour'].data_ptr() + 16 * K * o
+                c.detour_scores = out['detour_scores'].data_ptr() + 8 * K * o
+            if given is not None and host[i] is not None:
+                c.given, c.given_info = d_rows.data_ptr() + 16 * int(goffs[i]), d_info.data_ptr() + 8 * i
+                c.given_cap, c.regret = len(host[i]), out['regret'].data_ptr() + 8 * int(goffs[i])
+        ctx.check(ctx.lib.svx_row_alternatives(ctx.h, ca, K, float(max_slack), _p(out['summary']), npairs))
+        self.alternatives, self._alt_keep = out, (ca, keep)   # alive as long as the batch
+        ctx.hold(self)
+        return out
+
     def run_widen(self, guard=0, max_width_over2=None, max_rounds=4):
         """run() followed by band doubling (svx_align_widen, include/svx.h): pairs whose path touches the band edge are
         searched again around that path in twice the band, up to `max_rounds` times and `max_width_over2` (default:
@@ -809,7 +868,7 @@ def align_batch(pairs, final_alignment_types, del_percentile_frac, width_over2, 
 
 def vecalign(vecs0, vecs1, final_alignment_types, del_percentile_frac, width_over2, max_size_full_dp,
              costs_sample_size, num_samps_for_norm, norms0=None, norms1=None, normalize_inputs_inplace=False,
-             full_stack=False, given=None, search="coarse_to_fine", return_slack=False):
+             full_stack=False, given=None, search="coarse_to_fine", return_slack=False, return_alternatives=False):
     """dp_utils.py:381-537.  Returns {0: {'final_alignments', 'alignment_scores', 'del_penalty',
     'size0', 'size1', 'alignment_types'}, d: {'del_penalty', 'size0', 'size1'} ...}; with full_stack=True every
     depth also carries the intermediates the reference keeps (n0, n1, searchpath, a_b_costs, b_offset, a_b_csum,
@@ -818,7 +877,9 @@ def vecalign(vecs0, vecs1, final_alignment_types, del_percentile_frac, width_ove
     stack[0]['given'] = dict(verdict, found_total, given_total, del_penalty, report, scores) (search_error()).
     search: "coarse_to_fine" (the reference) or "straight" (PreparedBatch: depth 0 only).
     return_slack: stack[0]['row_slack'] = float64 array, the slack of every final alignment (PreparedBatch.row_slack), and
-    stack[0]['slack_summary'] = (rows, rows with slack 0, rows with slack +inf, 0)."""
+    stack[0]['slack_summary'] = (rows, rows with slack 0, rows with slack +inf, 0).
+    return_alternatives: True, or a dict of PreparedBatch.row_alternatives' keyword arguments (max_detour, max_slack, given:
+    int rows [g, 4] whose regret is wanted): stack[0]['alternatives'] = alternatives_to_host() of the call."""
     if search != "coarse_to_fine":
         max_size_full_dp = 1 << 30
     pb = PreparedBatch([(vecs0, vecs1)], final_alignment_types, del_percentile_frac, width_over2, max_size_full_dp,
@@ -853,6 +914,11 @@ def vecalign(vecs0, vecs1, final_alignment_types, del_percentile_frac, width_ove
         sl, summ = pb.row_slack()
         stack[0]['row_slack'] = sl.cpu().numpy()[:len(alignments)].copy()
         stack[0]['slack_summary'] = tuple(int(v) for v in summ.cpu().numpy()[0])
+    if return_alternatives:
+        kw = dict(return_alternatives) if isinstance(return_alternatives, dict) else {}
+        if kw.get('given') is not None:
+            kw['given'] = [kw['given']]
+        stack[0]['alternatives'] = alternatives_to_host(pb.row_alternatives(**kw), len(alignments))
     if normalize_inputs_inplace:
         make_norm1(vecs0)
         make_norm1(vecs1)
@@ -1046,6 +1112,69 @@ def path_slack(a_b_costs, b_offset_in, alignment_types, del_penalty, x_in_size, 
     ctx.check(ctx.lib.svx_path_slack(ctx.h, _p(c), _p(bin_), A, B, types, T, float(del_penalty), int(x_in_size), int(y_in_size),
                                      _p(csum), _p(bsum), _p(drows), _p(cnt), n, _p(out)))
     return out.cpu().numpy()[:n].copy()
+
+
+def alternatives_to_host(alt, n_rows, offset=0, pair=0):
+    """One pair's share of PreparedBatch.row_alternatives' device tensors as numpy: slack, edge, span, summary, detours (per
+    row None, or (rows [k, 4], scores [k]) of a written detour) and, when asked for, regret."""
+    o = int(offset)
+    span = alt['span'][o:o + n_rows].cpu().numpy()
+    out = dict(slack=alt['slack'][o:o + n_rows].cpu().numpy(), edge=alt['edge'][o:o + n_rows].cpu().numpy(), span=span,
+               summary=tuple(int(v) for v in alt['summary'][pair].cpu().numpy()))
+    if 'detour' in alt:
+        det, sc = alt['detour'][o:o + n_rows].cpu().numpy(), alt['detour_scores'][o:o + n_rows].cpu().numpy()
+        out['detours'] = [(det[r, :span[r, 2]].copy(), sc[r, :span[r, 2]].copy()) if span[r, 3] == 0 else None for r in range(n_rows)]
+    if 'regret' in alt:
+        g = alt['given_offs']
+        out['regret'] = alt['regret'][int(g[pair]):int(g[pair + 1])].cpu().numpy()
+    return out
+
+
+def path_alternatives(a_b_costs, b_offset_in, alignment_types, del_penalty, x_in_size, y_in_size, a_b_csum, a_b_bsum, a_b_xp, a_b_yp,
+                      rows, max_detour=16, max_slack=float("inf"), given=None, detour=True):
+    """svx_path_alternatives (include/svx.h): the alternatives of int rows [n, 4] that form a path, on the planes a_b_csum,
+    a_b_xp, a_b_yp (sparse_dp) and a_b_bsum (sparse_dp_backward) -> dict of numpy arrays: slack [n], edge [n, 4], span [n,
+    4], detour [n, max_detour, 4] and detour_scores [n, max_detour] (-1 / NaN where nothing is written; absent with
+    detour=False), regret [len(given)] when given (int rows [g, 4]) is not None."""
+    from .dp_core import _typed, _types
+    ctx = _ctx()
+    t = ctx.torch
+    a_b_costs = _typed(a_b_costs, np.float32, 3, "a_b_costs")
+    b_offset_in = _typed(b_offset_in, np.int32, 1, "b_offset_in")
+    types, T = _types(alignment_types)
+    Tc, A, B = a_b_costs.shape
+    assert Tc == T
+    rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 4)
+    n, K = len(rows), int(max_detour)
+    planes = [_dev(ctx, np.ascontiguousarray(x, dtype=dt)) for x, dt in ((a_b_csum, np.float64), (a_b_bsum, np.float64),
+                                                                          (a_b_xp, np.int32), (a_b_yp, np.int32))]
+    assert all(tuple(x.shape) == (A + 2, B) for x in planes)
+    c = _dev(ctx, a_b_costs) if a_b_costs.size else t.empty(1, dtype=t.float32, device=ctx.tdev)
+    bin_ = _dev(ctx, b_offset_in)
+    drows = _dev(ctx, rows if n else np.zeros((1, 4), np.int32))
+    cnt = t.tensor([n], dtype=t.int32).to(ctx.tdev)
+    m = max(1, n)
+    out = dict(slack=t.full((m,), float("nan"), dtype=t.float64, device=ctx.tdev),
+               edge=t.full((m, 4), -1, dtype=t.int32, device=ctx.tdev), span=t.full((m, 4), -1, dtype=t.int32, device=ctx.tdev))
+    one = _lib.Alt()
+    one.slack, one.edge, one.span = out['slack'].data_ptr(), out['edge'].data_ptr(), out['span'].data_ptr()
+    if detour:
+        out['detour'] = t.full((m, max(1, K), 4), -1, dtype=t.int32, device=ctx.tdev)
+        out['detour_scores'] = t.full((m, max(1, K)), float("nan"), dtype=t.float64, device=ctx.tdev)
+        one.detour, one.detour_scores = out['detour'].data_ptr(), out['detour_scores'].data_ptr()
+    if given is not None:
+        g = np.ascontiguousarray(given, dtype=np.int32).reshape(-1, 4)
+        dg = _dev(ctx, g if len(g) else np.zeros((1, 4), np.int32))
+        dinfo = _dev(ctx, np.asarray([len(g), 0], np.int32))
+        out['regret'] = t.full((max(1, len(g)),), float("nan"), dtype=t.float64, device=ctx.tdev)
+        one.given, one.given_info, one.given_cap, one.regret = dg.data_ptr(), dinfo.data_ptr(), len(g), out['regret'].data_ptr()
+    ctx.check(ctx.lib.svx_path_alternatives(ctx.h, _p(c), _p(bin_), A, B, types, T, float(del_penalty), int(x_in_size), int(y_in_size),
+                                            _p(planes[0]), _p(planes[1]), _p(planes[2]), _p(planes[3]), _p(drows), _p(cnt), n,
+                                            ctypes.byref(one), K, float(max_slack)))
+    res = {k: v.cpu().numpy()[:n].copy() for k, v in out.items() if k != 'regret'}
+    if given is not None:
+        res['regret'] = out['regret'].cpu().numpy()[:len(g)].copy()
+    return res
 
 
 def make_search_path(alignments, size0=0, size1=0, upsample=False):

@@ -130,8 +130,11 @@ def align(src: str, tgt: str, src_embed: List[str], src_stopes: bool, tgt_stopes
           src_ignore_indices: Optional[Union[str, Path]] = None, tgt_ignore_indices: Optional[Union[str, Path]] = None,
           verbose: bool = False, debug_save_stack: Optional[str] = None, gold_alignment: Optional[str] = None,
           print_results: bool = False, save_aligned_text_to_file: Optional[str] = None, mode: str = "ref", band: int = 2048,
-          return_slack: bool = False):
+          return_slack: bool = False, return_alternatives=False):
     """Align one pair of documents (vecalign.py:198-293); returns the result stack.
+    return_alternatives: True or a dict (max_detour, max_slack, given): also stack[0]['alternatives'] -- per final alignment
+    the competing edge of its cut and the detour of the best path through it, and the regret of given rows
+    (svx_row_alternatives; PreparedBatch.row_alternatives) --, refused where return_slack is.
     return_slack: also stack[0]['row_slack'], the slack of every final alignment -- the total of the best path of the same
     band without that row minus the total of the returned path (svx_row_slack) -- and stack[0]['slack_summary']; a band above
     64 cells in the band / dense modes runs the tile sweep, which keeps no costs, and is refused."""
@@ -156,13 +159,13 @@ def align(src: str, tgt: str, src_embed: List[str], src_stopes: bool, tgt_stopes
                          del_percentile_frac=del_percentile_frac, width_over2=width_over2,
                          max_size_full_dp=max_size_full_dp, costs_sample_size=costs_sample_size,
                          num_samps_for_norm=num_samps_for_norm, full_stack=bool(debug_save_stack), given=gold_path,
-                         return_slack=return_slack)
-    elif gold_path is not None or return_slack:
+                         return_slack=return_slack, return_alternatives=return_alternatives)
+    elif gold_path is not None or return_slack or return_alternatives:
         w2 = max(3, (band + 1) // 2) if mode == "band" else max(int(src_vectors.shape[1]), int(tgt_vectors.shape[1])) + 1
         stack = vecalign(vecs0=src_vectors, vecs1=tgt_vectors, final_alignment_types=types,
                          del_percentile_frac=del_percentile_frac, width_over2=w2, max_size_full_dp=max_size_full_dp,
                          costs_sample_size=costs_sample_size, num_samps_for_norm=num_samps_for_norm, given=gold_path,
-                         search="straight", return_slack=return_slack)
+                         search="straight", return_slack=return_slack, return_alternatives=return_alternatives)
     else:
         from .dp_utils import align_band
         w2 = max(3, (band + 1) // 2) if mode == "band" else max(int(src_vectors.shape[1]), int(tgt_vectors.shape[1])) + 1
