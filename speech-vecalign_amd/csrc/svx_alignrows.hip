@@ -544,8 +544,6 @@ void rows_fill_pair(RowsPair& r, const svx_pair& q, int p, RowsChunk* hc, long l
     }
 }
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int svx_alignment_rows(svx_ctx* ctx, int dtype, int d, const svx_pair* pairs, int n_pairs, double max_score, int64_t cap,

@@ -359,7 +359,7 @@ struct Bump {
     size_t off = 0;
     size_t take(size_t bytes) {
         size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
+        off += up256(bytes);
         return o;
     }
 };
@@ -652,29 +652,25 @@ extern "C" int svx_debug_level(svx_ctx* ctx, int pair, int level, svx_level_view
     return SVX_OK;
 }
 
-// The host mirrors of the last batch's descriptors, first half then second (svx_contact.hip); false when there is none.
-bool svxl_last_batch(svx_ctx* ctx, const SvxPairDev** host, int* n_pairs, int* band) {
+// The last batch call for the post-processing entries (svx_common.h); both halves of a pipelined call were planned with the
+// same parameters.
+int svxl_last_call(svx_ctx* ctx, const char* who, int n_pairs, const char* needs_costs, SvxLastCall* out) {
     svx_ctx_ext* cx = X(ctx);
-    if (!cx->last_ok) return false;
-    host[0] = cx->half[0].host.data();
-    n_pairs[0] = cx->half[0].n_pairs;
-    const bool two = cx->last_split > 0;
-    host[1] = two ? cx->half[1].host.data() : nullptr;
-    n_pairs[1] = two ? cx->half[1].n_pairs : 0;
-    *band = cx->last_band;
-    return true;
-}
-
-// What svxl_last_batch does not hand out: the call's storage type, its embedding dimension and its level-0 type set (both
-// halves of a pipelined call were planned with the same parameters).
-bool svxl_last_batch_types(svx_ctx* ctx, int* dtype, int* d, const SvxTypes** types) {
-    svx_ctx_ext* cx = X(ctx);
-    if (!cx->last_ok) return false;
+    const bool two = cx->last_ok && cx->last_split > 0;
     const BatchParams& bp = cx->half[0].bp;
-    *dtype = bp.dtype;
-    *d = bp.d;
-    *types = &bp.tfinal;
-    return true;
+    out->half[0] = cx->half[0].host.data();
+    out->half[1] = two ? cx->half[1].host.data() : nullptr;
+    out->n_first = cx->half[0].n_pairs;
+    out->n_pairs = cx->last_ok ? out->n_first + (two ? cx->half[1].n_pairs : 0) : 0;
+    out->band = cx->last_band; out->dtype = bp.dtype; out->d = bp.d; out->types = &bp.tfinal;
+    NEED(ctx, out->n_pairs > 0, "%s: no earlier svx_align_batch / svx_align_around call on this context", who);
+    NEED(ctx, n_pairs < 0 || n_pairs == out->n_pairs, "%s: %d pairs given, the last call had %d", who, n_pairs, out->n_pairs);
+    for (int p = 0; needs_costs && p < out->n_pairs; p++)
+        NEED(ctx, out->pair(p).lev[0].costs,
+             "%s: the last call ran the tile sweep, which keeps no cost array (a_b_costs is NULL): %s a band of at most 64 cells in the "
+             "straight and around-wide modes", who, needs_costs);
+    SVX_HIP(ctx, hipSetDevice(ctx->device));
+    return svx_flush(ctx);
 }
 
 // ------------------------------------------------------------------------------ plan of one half

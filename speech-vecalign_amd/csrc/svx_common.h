@@ -256,9 +256,9 @@ struct svx_ctx {
     // offsets, compacted rows), svx_knn_search_groups (svx_groupsearch.hip: offsets, workgroup table) and svx_time_prior
     // (svx_prior.hip: descriptors, prefix counts), svx_band_contact and svx_align_widen (svx_contact.hip: descriptors, the
     // report rows, the staged priors of a round), svx_score_alignments (svx_given.hip: descriptors, chunk table, partial sums)
-    // svx_row_slack (svx_slack.hip: descriptors, one backward plane per pair) and svx_row_alternatives / svx_path_alternatives
-    // (svx_alt.hip: descriptors, per pair one backward plane and one node table).  They go through svxl_scratch_begin /
-    // svxl_scratch_upload only.
+    // svx_row_slack (svx_slack.hip: one array of PlanePair descriptors, svx_plane.h, then one backward plane per pair) and
+    // svx_row_alternatives / svx_path_alternatives (svx_alt.hip: the same one array, then per pair one backward plane and one
+    // node table).  They go through svxl_scratch_begin / svxl_scratch_upload only.
     char* post_buf;
     size_t post_bytes;        // counted in svx_scratch_bytes
     char* post_pin[2];
@@ -272,6 +272,7 @@ int svx_fail(svx_ctx* ctx, int code, const char* fmt, ...);
 #define NEED(ctx, cond, ...) \
     do { if (!(cond)) return svx_fail(ctx, SVX_ERR_ARG, __VA_ARGS__); } while (0)
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }   // every piece of a scratch layout starts on 256 bytes
 #define SVX_HIP(ctx, call)                                                                     \
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \
@@ -339,33 +340,30 @@ int svxl_del_penalty(svx_ctx*, const float* scores, int64_t n, double frac, doub
 int svxl_del_penalty_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int max_levels, double frac);
 // prior alignments (svx_prior.hip)
 int svxl_prior_ingest_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs);
-// band contact (svx_contact.hip reads the descriptors of the last batch: svx_api.hip)
-bool svxl_last_batch(svx_ctx*, const SvxPairDev** host, int* n_pairs, int* band);
-// storage type, embedding dimension and level-0 type set of that same call (svx_given.hip); false when there is none
-bool svxl_last_batch_types(svx_ctx*, int* dtype, int* d, const SvxTypes** types);
-// row slack (svx_slack.hip): the per-pair descriptor of its kernels, the backward band DP and the slack of the rows of a
-// path, per-op
-struct SlackPair {
-    const float* costs;
-    const int* boff_in;     // [A]
-    const int* path_len;    // device A (the pipeline), or null: A below
-    const double* pen_dev;  // device penalty (the pipeline), or null: pen below
-    const int* status;      // the aligner's info[1] of the pair, or null
-    const double* csum;     // [A+2][B] forward plane (k_path_slack only)
-    double* bsum;           // [A+2][B] backward plane; null: the pair is skipped
-    const int* rows;        // [cap][4]
-    const int* n_rows;      // [1]
-    double* slack;          // [cap]
-    int* summary;           // [4] or null (per-op entry)
-    double pen;
-    int A, xs, ys, cap;
+// The context's last svx_align_batch / svx_align_around call, for the entries that post-process what it left on the device
+// (svx_api.hip): svx_band_contact / svx_align_widen, svx_score_alignments, svx_row_slack, svx_row_alternatives.
+struct SvxLastCall {
+    const SvxPairDev* half[2];  // the host mirrors of its descriptors, first half then second
+    int n_first;                // pairs of the first half
+    int n_pairs, band, dtype, d;
+    const SvxTypes* types;      // the level-0 type set
+    const SvxPairDev& pair(int p) const { return p < n_first ? half[0][p] : half[1][p - n_first]; }
 };
+// Fills *out, or fails with `who` in the text: no such call; n_pairs >= 0 is not its pair count; needs_costs (the head of the
+// text's last clause, "row slack needs") is given and the call kept no level-0 cost array.  Then selects the device and
+// flushes the software pipeline, behind which the call's second half is complete.
+int svxl_last_call(svx_ctx*, const char* who, int n_pairs, const char* needs_costs, SvxLastCall* out);
+// row slack (svx_slack.hip) and row alternatives (svx_alt.hip) share one per-pair descriptor, PlanePair (svx_plane.h).
+// The backward band DP and the slack of the rows of a path, per-op
+struct PlanePair;
 int svxl_sparse_dp_backward(svx_ctx*, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen,
                             int xs, int ys, double* bsum);
 int svxl_path_slack(svx_ctx*, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen, int xs,
                     int ys, const double* csum, const double* bsum, const int* rows, const int* n_rows, int cap, double* slack);
 // the backward sweep of n pairs over device descriptors (a pair with bsum == null is skipped); atb: costs are [A][T][B]
-int svxl_backward_batch(svx_ctx*, const SlackPair* dev, int n, const SvxTypes& types, int B, int atb);
+int svxl_backward_batch(svx_ctx*, const PlanePair* dev, int n, const SvxTypes& types, int B, int atb);
+// what a batch entry takes from the aligner's own record of a pair; the outputs are the entry's to add
+void svxl_plane_pair(PlanePair& r, const SvxPairDev& P, int32_t* summary);
 // row alternatives (svx_alt.hip), per-op: the arguments are checked there
 int svxl_path_alternatives(svx_ctx*, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen, int xs,
                            int ys, const double* csum, const double* bsum, const int* xp, const int* yp, const int* rows, const int* n_rows,

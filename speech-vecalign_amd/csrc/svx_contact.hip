@@ -140,21 +140,15 @@ __global__ __launch_bounds__(256) void k_stage_prior(const StagePair* __restrict
     if (threadIdx.x == 0) { gst(P.dst_info, count); gst(P.dst_info + 1, code); }
 }
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // svx_band_contact.  out == nullptr: the rows go to the scratch behind the descriptors and *out_scratch points at them
 // (svx_align_widen reads them back from there).
 int contact_impl(svx_ctx* ctx, const char* who, int level, int guard, int32_t* out, int32_t** out_scratch) {
-    const SvxPairDev* host[2] = {nullptr, nullptr};
-    int np[2] = {0, 0}, band = 0;
-    const bool have = svxl_last_batch(ctx, host, np, &band);
-    NEED(ctx, have && np[0] + np[1] > 0, "%s: no earlier svx_align_batch / svx_align_around call on this context", who);
     NEED(ctx, level >= 0, "%s: level %d", who, level);
     NEED(ctx, guard >= 0, "%s: guard %d", who, guard);
-    SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_flush(ctx);
+    SvxLastCall lc;
+    int rc = svxl_last_call(ctx, who, -1, nullptr, &lc);
     if (rc) return rc;
-    const int n_pairs = np[0] + np[1];
+    const int n_pairs = lc.n_pairs;
     const size_t b_up = up256((size_t)n_pairs * sizeof(ContactPair));
     const size_t b_all = b_up + (out ? 0 : up256((size_t)n_pairs * 4 * sizeof(int32_t)));
     char *pin, *dev;
@@ -162,28 +156,25 @@ int contact_impl(svx_ctx* ctx, const char* who, int level, int guard, int32_t* o
     if (rc) return rc;
     int32_t* dst = out ? out : reinterpret_cast<int32_t*>(dev + b_up);
     ContactPair* hp = reinterpret_cast<ContactPair*>(pin);
-    int p = 0;
-    for (int h = 0; h < 2; h++) {
-        for (int i = 0; i < np[h]; i++, p++) {
-            const SvxPairDev& P = host[h][i];
-            ContactPair& r = hp[p];
-            const bool refined = level <= P.L && (level < P.L || P.L == 0);
-            const SvxLevel& Lv = P.lev[refined ? level : 0];
-            r.align = Lv.align;
-            r.n_align = Lv.n_align;
-            r.boff_out = Lv.boff_out;
-            r.path_len = Lv.path_len;
-            r.status = P.status;
-            r.out = dst + 4 * (size_t)p;
-            r.size0 = Lv.n[0];
-            r.size1 = Lv.n[1];
-            r.rows_cap = Lv.n[0] + Lv.n[1] + 2;
-            r.refined = refined ? 1 : 0;
-        }
+    for (int p = 0; p < n_pairs; p++) {
+        const SvxPairDev& P = lc.pair(p);
+        ContactPair& r = hp[p];
+        const bool refined = level <= P.L && (level < P.L || P.L == 0);
+        const SvxLevel& Lv = P.lev[refined ? level : 0];
+        r.align = Lv.align;
+        r.n_align = Lv.n_align;
+        r.boff_out = Lv.boff_out;
+        r.path_len = Lv.path_len;
+        r.status = P.status;
+        r.out = dst + 4 * (size_t)p;
+        r.size0 = Lv.n[0];
+        r.size1 = Lv.n[1];
+        r.rows_cap = Lv.n[0] + Lv.n[1] + 2;
+        r.refined = refined ? 1 : 0;
     }
     rc = svxl_scratch_upload(ctx, (size_t)n_pairs * sizeof(ContactPair));
     if (rc) return rc;
-    hipLaunchKernelGGL(k_band_contact, dim3(n_pairs), dim3(256), 0, ctx->stream, reinterpret_cast<const ContactPair*>(dev), band, guard);
+    hipLaunchKernelGGL(k_band_contact, dim3(n_pairs), dim3(256), 0, ctx->stream, reinterpret_cast<const ContactPair*>(dev), lc.band, guard);
     SVX_LAUNCH_CHECK(ctx, "k_band_contact");
     if (out_scratch) *out_scratch = dst;
     return SVX_OK;

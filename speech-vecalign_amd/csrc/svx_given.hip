@@ -256,20 +256,12 @@ __global__ __launch_bounds__(256) void k_given_pairs(const GivenPair* __restrict
     }
 }
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int svx_score_alignments(svx_ctx* ctx, const svx_given* given, int n_pairs) {
     if (!ctx) return svx_fail(nullptr, SVX_ERR_ARG, "svx_score_alignments: ctx is NULL");
     NEED(ctx, given, "svx_score_alignments: given is NULL");
     NEED(ctx, n_pairs >= 0, "svx_score_alignments: negative n_pairs");
-    const SvxPairDev* host[2] = {nullptr, nullptr};
-    int np[2] = {0, 0}, band = 0, dtype = 0, d = 0;
-    const SvxTypes* types = nullptr;
-    const bool have = svxl_last_batch(ctx, host, np, &band) && svxl_last_batch_types(ctx, &dtype, &d, &types);
-    NEED(ctx, have && np[0] + np[1] > 0, "svx_score_alignments: no earlier svx_align_batch / svx_align_around call on this context");
-    NEED(ctx, n_pairs == np[0] + np[1], "svx_score_alignments: %d pairs given, the last call had %d", n_pairs, np[0] + np[1]);
     long long n_chunks = 0;
     for (int p = 0; p < n_pairs; p++) {
         const svx_given& g = given[p];
@@ -281,8 +273,8 @@ extern "C" int svx_score_alignments(svx_ctx* ctx, const svx_given* given, int n_
         n_chunks += ((long long)g.cap + SVX_GV_CHUNK - 1) / SVX_GV_CHUNK;
     }
     NEED(ctx, n_chunks <= 0x7fffffffLL, "svx_score_alignments: %lld chunks of rows", n_chunks);
-    SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_flush(ctx);  // with the software pipeline on, the call's second half is complete only behind this
+    SvxLastCall lc;
+    int rc = svxl_last_call(ctx, "svx_score_alignments", n_pairs, nullptr, &lc);
     if (rc) return rc;
     // ---- scratch: [descriptors][chunk table] uploaded, then [chunk parts]
     const size_t b_desc = up256((size_t)n_pairs * sizeof(GivenPair)), b_tab = up256((size_t)n_chunks * sizeof(GivenChunk));
@@ -294,27 +286,24 @@ extern "C" int svx_score_alignments(svx_ctx* ctx, const svx_given* given, int n_
     GivenPair* hp = reinterpret_cast<GivenPair*>(pin);
     GivenChunk* hc = reinterpret_cast<GivenChunk*>(pin + b_desc);
     long long at = 0;
-    int p = 0;
-    for (int h = 0; h < 2; h++) {
-        for (int i = 0; i < np[h]; i++, p++) {
-            const SvxPairDev& P = host[h][i];
-            const SvxLevel& Lv = P.lev[0];
-            const svx_given& g = given[p];
-            GivenPair& r = hp[p];
-            for (int s = 0; s < 2; s++) { r.v[s] = P.v[s]; r.nrm[s] = Lv.nrm[s]; r.inv[s] = Lv.inv[s]; }
-            r.pen = Lv.pen;
-            r.boff_out = Lv.boff_out;
-            r.path_len = Lv.path_len;
-            r.status = P.status;
-            r.rows = g.rows; r.info = g.info; r.scores = g.scores; r.total = g.total; r.report = g.report;
-            r.n = Lv.n[0]; r.m = Lv.n[1]; r.k0 = P.K[0]; r.k1 = P.K[1];
-            r.cap = g.rows ? g.cap : 0;
-            r.first_chunk = (int)at;
-            for (int first = 0; first < r.cap; first += SVX_GV_CHUNK) {
-                hc[at].pair = p;
-                hc[at].first = first;
-                at++;
-            }
+    for (int p = 0; p < n_pairs; p++) {
+        const SvxPairDev& P = lc.pair(p);
+        const SvxLevel& Lv = P.lev[0];
+        const svx_given& g = given[p];
+        GivenPair& r = hp[p];
+        for (int s = 0; s < 2; s++) { r.v[s] = P.v[s]; r.nrm[s] = Lv.nrm[s]; r.inv[s] = Lv.inv[s]; }
+        r.pen = Lv.pen;
+        r.boff_out = Lv.boff_out;
+        r.path_len = Lv.path_len;
+        r.status = P.status;
+        r.rows = g.rows; r.info = g.info; r.scores = g.scores; r.total = g.total; r.report = g.report;
+        r.n = Lv.n[0]; r.m = Lv.n[1]; r.k0 = P.K[0]; r.k1 = P.K[1];
+        r.cap = g.rows ? g.cap : 0;
+        r.first_chunk = (int)at;
+        for (int first = 0; first < r.cap; first += SVX_GV_CHUNK) {
+            hc[at].pair = p;
+            hc[at].first = first;
+            at++;
         }
     }
     rc = svxl_scratch_upload(ctx, b_up);
@@ -325,12 +314,12 @@ extern "C" int svx_score_alignments(svx_ctx* ctx, const svx_given* given, int n_
     hipStream_t st = ctx->stream;
     if (n_chunks > 0) {
         const dim3 grid((unsigned)n_chunks), block(SVX_GV_CHUNK);
-        if (dtype == SVX_F32) k_given_rows<ElemF32><<<grid, block, 0, st>>>(dp, dc, *types, band, d, dparts);
-        else if (dtype == SVX_F16) k_given_rows<ElemF16><<<grid, block, 0, st>>>(dp, dc, *types, band, d, dparts);
-        else k_given_rows<ElemBF16><<<grid, block, 0, st>>>(dp, dc, *types, band, d, dparts);
+        if (lc.dtype == SVX_F32) k_given_rows<ElemF32><<<grid, block, 0, st>>>(dp, dc, *lc.types, lc.band, lc.d, dparts);
+        else if (lc.dtype == SVX_F16) k_given_rows<ElemF16><<<grid, block, 0, st>>>(dp, dc, *lc.types, lc.band, lc.d, dparts);
+        else k_given_rows<ElemBF16><<<grid, block, 0, st>>>(dp, dc, *lc.types, lc.band, lc.d, dparts);
         SVX_LAUNCH_CHECK(ctx, "k_given_rows");
     }
-    k_given_pairs<<<dim3((unsigned)n_pairs), dim3(256), 0, st>>>(dp, dparts, band);
+    k_given_pairs<<<dim3((unsigned)n_pairs), dim3(256), 0, st>>>(dp, dparts, lc.band);
     SVX_LAUNCH_CHECK(ctx, "k_given_pairs");
     return SVX_OK;
 }

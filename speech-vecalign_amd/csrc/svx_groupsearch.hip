@@ -291,7 +291,6 @@ extern "C" int svx_knn_search_groups(svx_ctx* ctx, const void* queries, int q_dt
     NEED(ctx, (n == 0 || (queries && sims && ids)) && (n_db == 0 || db), "svx_knn_search_groups: null argument");
     if (n_blocks == 0) return SVX_OK;
     // ---- post-processing scratch: [q_off][db_off][workgroup table], all of it uploaded
-    auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_off = up256((size_t)(n_groups + 1) * sizeof(long long)), b_tab = up256((size_t)n_blocks * sizeof(GroupBlock));
     const size_t b_up = 2 * b_off + b_tab;
     char *pin, *dev;

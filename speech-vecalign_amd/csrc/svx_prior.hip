@@ -256,7 +256,6 @@ extern "C" int svx_time_prior(svx_ctx* ctx, const svx_pair* pairs, const svx_fra
     NEED(ctx, window > 0, "svx_time_prior: window must be positive (got %lld)", (long long)window);
     NEED(ctx, lag > -(1ll << 62) && lag < (1ll << 62), "svx_time_prior: lag %lld out of range", (long long)lag);
     if (n_pairs == 0) return SVX_OK;
-    auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
     size_t ints = 0;
     for (int p = 0; p < n_pairs; p++) {
         const svx_pair& q = pairs[p];

@@ -17,55 +17,23 @@
 //   k_bk_wide      any B: cells strided over the workgroup, per-(diagonal, move) shifts and ring slots tabulated 32
 //                  diagonals at a time, costs from global memory; RING keeps maxstep+1 diagonals of Bk in LDS, otherwise
 //                  they are re-read from the output plane (the workgroup's own stores), as k_sparse_dp<RING> does.
-//   k_path_slack   one workgroup per pair over a stored Bk plane; a wave takes a row at a time.  The cut behind the row's
-//                  start diagonal c is crossed by the edges into diagonals c+1 .. c+maxstep: lanes take (diagonal, cell)
-//                  targets, loop over the moves that reach back to c or further, and price (F(u) + w) + Bk(v) from three
-//                  resident reads; a wave minimum, then slack = alt - total.  The band offsets of the 2 * maxstep diagonals
-//                  such an edge can touch are put into a per-wave LDS table once per row.  A row that fails the range
-//                  checks forms no address.  The counts of the summary are reduced through LDS.
-// Both cost layouts are read: [T][A][B] (per-op) and [A][T][B] (fused pipeline).  Plain C++, vector stores only.
-#include "svx_common.h"
+//   k_path_slack   one workgroup per pair over a stored Bk plane; a wave takes a row at a time: the cut scan of svx_plane.h
+//                  (cut_scan<false>: the minimum of (F(u) + w) + Bk(v) over the edges that cross the cut behind the row's
+//                  start diagonal, the row's own left out), then slack = alt - total.  A row that fails the range checks
+//                  forms no address.  The counts of the summary are reduced through LDS.
+// The descriptor of a pair (PlanePair), its geometry and the helpers that read a plane are svx_plane.h's, shared with
+// svx_alt.hip.  svx_row_slack lays out the post-processing scratch as [descriptors] uploaded, then one Bk plane per pair that
+// is not skipped.  Both cost layouts are read: [T][A][B] (per-op) and [A][T][B] (fused pipeline).  Plain C++, vector stores only.
+#include "svx_plane.h"
 
 namespace {
-
-struct BkArgs {
-    const float* costs;
-    const int* boff_in;
-    int A, B;
-    double pen;
-    int xs, ys;
-    double* bsum;
-    int atb;
-};
-
-__device__ __forceinline__ bool bk_args(const SlackPair& P, int B, int atb, BkArgs* g) {
-    if (!P.bsum) return false;
-    if (P.status && gld(P.status) != 0) return false;
-    g->A = P.path_len ? gld(P.path_len) : P.A;
-    if (g->A <= 0) return false;
-    g->costs = P.costs;
-    g->boff_in = P.boff_in;
-    g->B = B;
-    g->pen = P.pen_dev ? gld(P.pen_dev) : P.pen;
-    g->xs = P.xs;
-    g->ys = P.ys;
-    g->bsum = P.bsum;
-    g->atb = atb;
-    return true;
-}
-
-__device__ __forceinline__ size_t bk_cost_index(const BkArgs& g, int T, int t, int a, int b) {
-    return g.atb ? ((size_t)a * T + t) * g.B + b : ((size_t)t * g.A + a) * g.B + b;
-}
-// b_offset_out[a], 0 <= a < A + 2
-__device__ __forceinline__ int bk_bout(const int* boff_in, int a) { return a < 2 ? gld(boff_in) : gld(boff_in + (a - 2)) + 1; }
 
 // ------------------------------------------------------------------------------ backward sweep, any band width
 constexpr int BKW_CH = 32;
 __host__ __device__ inline size_t bkw_tab_bytes(int NTt) { return (size_t)BKW_CH * (2 * NTt + 1) * sizeof(int) + (size_t)NTt * sizeof(int); }
 
 template <bool RING>
-__device__ void bk_block(const BkArgs& g, const SvxTypes& ty, double* ring, int* tab) {
+__device__ void bk_block(const PlaneGeo& g, const SvxTypes& ty, double* ring, int* tab) {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int B = g.B, Aout = g.A + 2;
     const int T = ty.n, NTt = ty.n + 2;
@@ -84,13 +52,13 @@ __device__ void bk_block(const BkArgs& g, const SvxTypes& ty, double* ring, int*
             const int av = a + st;
             int v = 1 << 24, sl = 0;  // no successor diagonal: the shift pushes the cell out of the band
             if (av < Aout) {
-                v = bk_bout(g.boff_in, a) + yo - bk_bout(g.boff_in, av);
+                v = plane_bout(g.boff_in, a) + yo - plane_bout(g.boff_in, av);
                 sl = av % RD;
             }
             shs[e] = v;
             sls[e] = sl;
         }
-        for (int i = tid; i < BKW_CH; i += nt) bos[i] = a0 + i < Aout ? bk_bout(g.boff_in, a0 + i) : 0;
+        for (int i = tid; i < BKW_CH; i += nt) bos[i] = a0 + i < Aout ? plane_bout(g.boff_in, a0 + i) : 0;
         __syncthreads();
         const int a_end = a0 + BKW_CH < Aout ? a0 + BKW_CH : Aout;
         for (int a = a_end - 1; a >= a0; a--) {
@@ -109,7 +77,7 @@ __device__ void bk_block(const BkArgs& g, const SvxTypes& ty, double* ring, int*
                     const int xo = pk & 255, yo = (pk >> 8) & 255, st = pk >> 16;
                     const int bv = b + sh[t];
                     const bool ok = lattice && xx + xo <= g.xs && yy + yo <= g.ys && 0 <= bv && bv < B;
-                    const size_t ci = (ok && t < T) ? bk_cost_index(g, T, t, a + st - 2, bv) : 0;
+                    const size_t ci = (ok && t < T) ? plane_cost_index(g, t, a + st - 2, bv) : 0;
                     const double w = t < T ? (double)g.costs[ci] : g.pen;
                     const double nxt = RING ? ring[ok ? sl[t] * B + bv : 0] : g.bsum[ok ? (size_t)(a + st) * B + bv : 0];
                     const double tot = w + nxt;
@@ -144,7 +112,7 @@ __host__ __device__ inline size_t bkf_smem_bytes(int T, int B, int RD, int CH) {
 // << 2 | lane of the (1,0) successor << 9.
 // Stage chunk q (diagonals a0 = q * CH .. a0 + CH - 1) into buffer q & 1.  Every staging wave first copies the band offsets
 // of diagonals a0 .. a0 + CH + RD - 1 into its own small LDS table.  wboff: [4 waves][CH + RD] ints.
-__device__ __forceinline__ void bkf_stage(const BkArgs& g, const int* tpk, int T, int RD, int CH, int q, char* bufs, int* wboff,
+__device__ __forceinline__ void bkf_stage(const PlaneGeo& g, const int* tpk, int T, int RD, int CH, int q, char* bufs, int* wboff,
                                           int tsub, int nsub) {
     const int B = g.B, Aout = g.A + 2;
     const int a0 = q * CH;
@@ -159,11 +127,9 @@ __device__ __forceinline__ void bkf_stage(const BkArgs& g, const int* tpk, int T
     int* wb = wboff + ((threadIdx.x >> 6) & 3) * (CH + RD);
     for (int k = threadIdx.x & 63; k < CH + RD; k += 64) {
         const int a = a0 + k;
-        wb[k] = bk_bout(g.boff_in, a > lim ? lim : a);   // (past the last diagonal: never used, the moves are cut at lim)
+        wb[k] = plane_bout(g.boff_in, a > lim ? lim : a);   // (past the last diagonal: never used, the moves are cut at lim)
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // one thread per column -- a (type, cell) pair or, past those, a node cell -- walking the chunk's diagonals; with fewer
     // columns than staging threads the diagonals are split over thread groups
     const int ncols = TB + B;
@@ -196,7 +162,7 @@ __device__ __forceinline__ void bkf_stage(const BkArgs& g, const int* tpk, int T
                 const int bv = yy + yo - wb[i + st];
                 const bool ok = lattice && av <= lim && xx + xo <= g.xs && yy + yo <= g.ys && 0 <= bv && bv < B;
                 float cv = 0.f;
-                if (ok) cv = gld(g.costs + bk_cost_index(g, T, t, av - 2, bv));
+                if (ok) cv = gld(g.costs + plane_cost_index(g, t, av - 2, bv));
                 cost[i * TB + col] = cv;
                 idx[i * TB + col] = (unsigned short)(ok ? (av % RD) * B + bv : dummy);
             }
@@ -204,13 +170,13 @@ __device__ __forceinline__ void bkf_stage(const BkArgs& g, const int* tpk, int T
     }
 }
 
-__device__ __forceinline__ void bkf_flush(const BkArgs& g, const char* obuf, int B, int a0, int a_end, int tsub, int nsub) {
+__device__ __forceinline__ void bkf_flush(const PlaneGeo& g, const char* obuf, int B, int a0, int a_end, int tsub, int nsub) {
     const double* ob = reinterpret_cast<const double*>(obuf);
     const int n = (a_end - a0) * B;
     for (int e = tsub; e < n; e += nsub) gst(g.bsum + ((size_t)a0 * B + e), ob[e]);
 }
 
-__device__ void bk_fast(const BkArgs& g, const SvxTypes& ty, int CH, char* smem) {
+__device__ void bk_fast(const PlaneGeo& g, const SvxTypes& ty, int CH, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int A = __builtin_amdgcn_readfirstlane(g.A), B = g.B, Aout = A + 2, T = ty.n, NTt = ty.n + 2, RD = ty.maxstep + 1;
@@ -293,22 +259,22 @@ __device__ void bk_fast(const BkArgs& g, const SvxTypes& ty, int CH, char* smem)
     bkf_flush(g, obufs, B, 0, CH < Aout ? CH : Aout, tid, BKF_THREADS);   // chunk 0 sits in buffer 0
 }
 
-__global__ __launch_bounds__(BKF_THREADS) void k_bk_fast(const SlackPair* __restrict__ pairs, SlackPair one, int use_one, SvxTypes ty,
+__global__ __launch_bounds__(BKF_THREADS) void k_bk_fast(const PlanePair* __restrict__ pairs, PlanePair one, int use_one, SvxTypes ty,
                                                          int B, int atb, int CH) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const SlackPair P = use_one ? one : pairs[blockIdx.x];
-    BkArgs g;
-    if (!bk_args(P, B, atb, &g)) return;   // (uniform)
+    const PlanePair P = use_one ? one : pairs[blockIdx.x];
+    PlaneGeo g;
+    if (!P.bsum || !plane_geo(P, ty, B, atb, &g)) return;   // (uniform) a skipped or failed pair
     bk_fast(g, ty, CH, smem);
 }
 
 template <bool RING>
-__global__ __launch_bounds__(1024) void k_bk_wide(const SlackPair* __restrict__ pairs, SlackPair one, int use_one, SvxTypes ty, int B,
+__global__ __launch_bounds__(1024) void k_bk_wide(const PlanePair* __restrict__ pairs, PlanePair one, int use_one, SvxTypes ty, int B,
                                                   int atb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const SlackPair P = use_one ? one : pairs[blockIdx.x];
-    BkArgs g;
-    if (!bk_args(P, B, atb, &g)) return;   // (uniform)
+    const PlanePair P = use_one ? one : pairs[blockIdx.x];
+    PlaneGeo g;
+    if (!P.bsum || !plane_geo(P, ty, B, atb, &g)) return;   // (uniform) a skipped or failed pair
     const size_t ring_bytes = RING ? (((size_t)(ty.maxstep + 1) * B * sizeof(double) + 15) & ~(size_t)15) : 0;
     bk_block<RING>(g, ty, reinterpret_cast<double*>(smem), reinterpret_cast<int*>(smem + ring_bytes));
 }
@@ -316,117 +282,35 @@ __global__ __launch_bounds__(1024) void k_bk_wide(const SlackPair* __restrict__ 
 // ------------------------------------------------------------------------------ slack of the rows of a path
 constexpr int SK_THREADS = 512;
 constexpr int SK_WAVES = SK_THREADS / SVX_WAVE;
-constexpr int SK_MAXSTEP = 200;   // make_types: type sizes are at most 100 a side
 
-__global__ __launch_bounds__(SK_THREADS) void k_path_slack(const SlackPair* __restrict__ pairs, SlackPair one, int use_one, SvxTypes ty,
+__global__ __launch_bounds__(SK_THREADS) void k_path_slack(const PlanePair* __restrict__ pairs, PlanePair one, int use_one, SvxTypes ty,
                                                            int B, int atb) {
     __shared__ int scnt[SK_WAVES][2];
-    __shared__ int sbo[SK_WAVES][2 * SK_MAXSTEP];   // per wave: b_offset_out of diagonals c - maxstep + 1 .. c + maxstep of its row
-    const SlackPair P = use_one ? one : pairs[blockIdx.x];
+    __shared__ int sbo[SK_WAVES][2 * MAXSTEP];   // per wave: b_offset_out of diagonals c - maxstep + 1 .. c + maxstep of its row
+    const PlanePair P = use_one ? one : pairs[blockIdx.x];
     if (!P.slack) return;   // (uniform) a skipped pair: nothing of it is written
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    BkArgs g;
-    const bool ok_pair = bk_args(P, B, atb, &g);
-    int cnt = ok_pair ? gld(P.n_rows) : -1;
-    if (P.summary) {
-        if (cnt < 0 || cnt > P.cap) {   // (uniform) a failed pair
-            if (tid == 0) gst16(P.summary, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-            return;
-        }
-    } else {
-        if (!ok_pair) return;
-        cnt = cnt < 0 ? 0 : (cnt > P.cap ? P.cap : cnt);
-    }
-    const int T = ty.n, NTt = ty.n + 2;
-    const long long Aout = (long long)g.A + 2;
-    const long long xs = g.xs, ys = g.ys;
+    PlaneGeo g;
+    const bool ok_pair = P.bsum && plane_geo(P, ty, B, atb, &g);
+    int cnt;
+    if (!plane_row_count(P, ok_pair, &cnt)) return;   // (uniform) a failed pair
     const double inf = __builtin_inf();
-    // total = F(end); +inf when the end node is no band cell
-    double total = inf;
-    if (xs >= 0 && ys >= 0 && xs + ys < Aout) {
-        const long long be = ys - bk_bout(g.boff_in, (int)(xs + ys));
-        if (be >= 0 && be < B) total = gld(P.csum + ((size_t)(xs + ys) * B + be));
-    }
+    const double total = plane_total(g);
     int n_zero = 0, n_inf = 0;   // lane 0 of the wave counts
-    const int items = ty.maxstep * B;
     for (int r = w; r < cnt; r += SK_WAVES) {
         const uint4 rv = gld16(P.rows + 4 * (size_t)r);
-        const long long x0 = (int)rv.x, xl = (int)rv.y, y0 = (int)rv.z, yl = (int)rv.w;
-        const long long c = x0 + y0;
-        // ---- is the row an edge of the search space?  (no address is formed before the ranges are known to hold)
-        bool valid = x0 >= 0 && xl >= 0 && y0 >= 0 && yl >= 0 && x0 + xl <= xs && y0 + yl <= ys && xl + yl >= 1 && c + xl + yl < Aout;
-        if (valid) {
-            bool is_move = false;
-            for (int t = 0; t < NTt; t++)
-                if (ty.x[t] == xl && ty.y[t] == yl) is_move = true;
-            valid = is_move;
-        }
-        long long bu = 0;
-        if (valid) {
-            bu = y0 - bk_bout(g.boff_in, (int)c);
-            const long long bv = y0 + yl - bk_bout(g.boff_in, (int)(c + xl + yl));
-            valid = bu >= 0 && bu < B && bv >= 0 && bv < B;
-        }
+        int t_own, bui, bvi;
         double s = __builtin_nan("");
-        if (valid) {   // (uniform over the wave)
-            const int ci = (int)c, bui = (int)bu, xli = (int)xl, yli = (int)yl;
-            // the band offsets of every diagonal an edge across this cut can touch, once per row
-            const int ms = ty.maxstep, dbase = ci - ms + 1;
-            int* bo = sbo[w];
-            __builtin_amdgcn_wave_barrier();   // (the row before may still be reading the table)
-            for (int k = lane; k < 2 * ms; k += SVX_WAVE) {
-                const long long a = (long long)dbase + k;
-                bo[k] = (a >= 0 && a < Aout) ? bk_bout(g.boff_in, (int)a) : 0;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            double alt = inf;
-            for (int it = lane; it < items; it += SVX_WAVE) {
-                const int dv = it / B + 1, bv = it - (dv - 1) * B;
-                const long long avl = c + dv;
-                if (avl >= Aout) continue;
-                const int av = (int)avl;
-                const int vy = bv + bo[av - dbase], vx = av - vy;
-                if (vx < 0 || vx > xs || vy < 0 || vy > ys) continue;
-                const double bk = gld(P.bsum + ((size_t)av * B + bv));
-                for (int t = 0; t < NTt; t++) {
-                    const int xo = ty.x[t], yo = ty.y[t], st = xo + yo;
-                    if (st < dv) continue;             // the edge starts behind the cut
-                    const int au = av - st, ux = vx - xo, uy = vy - yo;
-                    if (au < 0 || ux < 0 || uy < 0) continue;
-                    const int bp = uy - bo[au - dbase];
-                    if (bp < 0 || bp >= B) continue;
-                    if (au == ci && bp == bui && xo == xli && yo == yli) continue;   // the row's own edge
-                    const double wgt = t < T ? (double)gld(g.costs + bk_cost_index(g, T, t, av - 2, bv)) : g.pen;
-                    const double cand = (gld(P.csum + ((size_t)au * B + bp)) + wgt) + bk;
-                    alt = cand < alt ? cand : alt;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const double other = __shfl_xor(alt, o, SVX_WAVE);
-                alt = other < alt ? other : alt;
-            }
-            s = alt - total;
-        }
+        if (plane_is_edge(g, ty, rv, &t_own, &bui, &bvi))   // (uniform over the wave)
+            s = cut_scan<false>(g, ty, sbo[w], (int)rv.x + (int)rv.z, bui, (int)rv.y, (int)rv.w, nullptr) - total;
         if (lane == 0) {
             gst(P.slack + r, s);
             n_zero += s == 0.0 ? 1 : 0;
             n_inf += s == inf ? 1 : 0;
         }
     }
-    if (!P.summary) return;
-    if (lane == 0) { scnt[w][0] = n_zero; scnt[w][1] = n_inf; }
-    __syncthreads();
-    if (tid == 0) {
-        int z = 0, f = 0;
-        for (int u = 0; u < SK_WAVES; u++) { z += scnt[u][0]; f += scnt[u][1]; }
-        gst16(P.summary, (uint32_t)cnt, (uint32_t)z, (uint32_t)f, 0u);
-    }
+    if (P.summary) plane_summary(scnt, P.summary, cnt, n_zero, n_inf, 0);
 }
-
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 inline int bk_threads(int B) {
     int t = ((B + 63) / 64) * 64;
@@ -446,7 +330,7 @@ int bkf_choose_ch(int T, int B, int maxstep) {
 }
 
 // the backward sweep of n pairs: `dev` descriptors, or the one descriptor `one` when dev is null
-int launch_backward(svx_ctx* ctx, const SlackPair* dev, const SlackPair& one, int n, const SvxTypes& types, int B, int atb) {
+int launch_backward(svx_ctx* ctx, const PlanePair* dev, const PlanePair& one, int n, const SvxTypes& types, int B, int atb) {
     const int use_one = dev ? 0 : 1;
     const int CH = bkf_choose_ch(types.n, B, types.maxstep);
     if (CH > 0) {
@@ -476,7 +360,7 @@ int launch_backward(svx_ctx* ctx, const SlackPair* dev, const SlackPair& one, in
 
 int svxl_sparse_dp_backward(svx_ctx* ctx, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen,
                             int xs, int ys, double* bsum) {
-    SlackPair one{};
+    PlanePair one{};
     one.costs = costs; one.boff_in = boff_in; one.bsum = bsum;
     one.pen = pen; one.A = A; one.xs = xs; one.ys = ys;
     return launch_backward(ctx, nullptr, one, 1, types, B, 0);
@@ -484,17 +368,36 @@ int svxl_sparse_dp_backward(svx_ctx* ctx, const float* costs, const int* boff_in
 
 int svxl_path_slack(svx_ctx* ctx, const float* costs, const int* boff_in, int A, int B, const SvxTypes& types, double pen, int xs,
                     int ys, const double* csum, const double* bsum, const int* rows, const int* n_rows, int cap, double* slack) {
-    SlackPair one{};
+    PlanePair one{};
     one.costs = costs; one.boff_in = boff_in; one.csum = csum; one.bsum = const_cast<double*>(bsum);   // (read only here)
     one.rows = rows; one.n_rows = n_rows; one.slack = slack;
     one.pen = pen; one.A = A; one.xs = xs; one.ys = ys; one.cap = cap;
-    hipLaunchKernelGGL(k_path_slack, dim3(1), dim3(SK_THREADS), 0, ctx->stream, (const SlackPair*)nullptr, one, 1, types, B, 0);
+    hipLaunchKernelGGL(k_path_slack, dim3(1), dim3(SK_THREADS), 0, ctx->stream, (const PlanePair*)nullptr, one, 1, types, B, 0);
     SVX_LAUNCH_CHECK(ctx, "k_path_slack");
     return SVX_OK;
 }
 
-int svxl_backward_batch(svx_ctx* ctx, const SlackPair* dev, int n, const SvxTypes& types, int B, int atb) {
-    return launch_backward(ctx, dev, SlackPair{}, n, types, B, atb);
+int svxl_backward_batch(svx_ctx* ctx, const PlanePair* dev, int n, const SvxTypes& types, int B, int atb) {
+    return launch_backward(ctx, dev, PlanePair{}, n, types, B, atb);
+}
+
+// What both batch entries put into a pair's descriptor from the aligner's own record of it.
+void svxl_plane_pair(PlanePair& r, const SvxPairDev& P, int32_t* summary) {
+    const SvxLevel& Lv = P.lev[0];
+    r = PlanePair{};
+    r.costs = Lv.costs;
+    r.boff_in = Lv.boff;
+    r.path_len = Lv.path_len;
+    r.pen_dev = Lv.pen;
+    r.status = P.status;
+    r.csum = Lv.csum;
+    r.xp = Lv.xp; r.yp = Lv.yp; r.bpk = Lv.bpk;
+    r.rows = Lv.align;
+    r.n_rows = Lv.n_align;
+    r.summary = summary;
+    r.xs = Lv.n[0];
+    r.ys = Lv.n[1];
+    r.cap = Lv.n[0] + Lv.n[1] + 2;
 }
 
 extern "C" int svx_row_slack(svx_ctx* ctx, double* const* slack, int32_t* summary, int n_pairs) {
@@ -502,66 +405,33 @@ extern "C" int svx_row_slack(svx_ctx* ctx, double* const* slack, int32_t* summar
     NEED(ctx, slack && summary, "svx_row_slack: null argument");
     NEED(ctx, aligned16(summary), "svx_row_slack: summary must be 16-byte aligned");
     NEED(ctx, n_pairs >= 0, "svx_row_slack: negative n_pairs");
-    const SvxPairDev* host[2] = {nullptr, nullptr};
-    int np[2] = {0, 0}, band = 0, dtype = 0, d = 0;
-    const SvxTypes* types = nullptr;
-    const bool have = svxl_last_batch(ctx, host, np, &band) && svxl_last_batch_types(ctx, &dtype, &d, &types);
-    NEED(ctx, have && np[0] + np[1] > 0, "svx_row_slack: no earlier svx_align_batch / svx_align_around call on this context");
-    NEED(ctx, n_pairs == np[0] + np[1], "svx_row_slack: %d pairs given, the last call had %d", n_pairs, np[0] + np[1]);
-    for (int h = 0; h < 2; h++)
-        for (int i = 0; i < np[h]; i++)
-            NEED(ctx, host[h][i].lev[0].costs,
-                 "svx_row_slack: the last call ran the tile sweep, which keeps no cost array (a_b_costs is NULL): row slack needs "
-                 "a band of at most 64 cells in the straight and around-wide modes");
-    SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_flush(ctx);  // with the software pipeline on, the call's second half is complete only behind this
+    SvxLastCall lc;
+    int rc = svxl_last_call(ctx, "svx_row_slack", n_pairs, "row slack needs", &lc);
     if (rc) return rc;
     // ---- scratch: [descriptors] uploaded, then one Bk plane per pair that is not skipped
-    const size_t b_desc = up256((size_t)n_pairs * sizeof(SlackPair));
+    const size_t b_desc = up256((size_t)n_pairs * sizeof(PlanePair));
     size_t b_all = b_desc;
-    {
-        int p = 0;
-        for (int h = 0; h < 2; h++)
-            for (int i = 0; i < np[h]; i++, p++)
-                if (slack[p]) b_all += up256(((size_t)host[h][i].lev[0].path_cap + 2) * band * sizeof(double));
-    }
+    for (int p = 0; p < n_pairs; p++)
+        if (slack[p]) b_all += up256(((size_t)lc.pair(p).lev[0].path_cap + 2) * lc.band * sizeof(double));
     char *pin, *dev;
     rc = svxl_scratch_begin(ctx, "svx_row_slack", b_desc, b_all, &pin, &dev);
     if (rc) return rc;
-    SlackPair* hp = reinterpret_cast<SlackPair*>(pin);
+    PlanePair* hp = reinterpret_cast<PlanePair*>(pin);
     size_t at = b_desc;
-    int p = 0;
-    for (int h = 0; h < 2; h++) {
-        for (int i = 0; i < np[h]; i++, p++) {
-            const SvxPairDev& P = host[h][i];
-            const SvxLevel& Lv = P.lev[0];
-            SlackPair& r = hp[p];
-            r = SlackPair{};
-            r.costs = Lv.costs;
-            r.boff_in = Lv.boff;
-            r.path_len = Lv.path_len;
-            r.pen_dev = Lv.pen;
-            r.status = P.status;
-            r.csum = Lv.csum;
-            r.rows = Lv.align;
-            r.n_rows = Lv.n_align;
-            r.slack = slack[p];
-            r.summary = summary + 4 * (size_t)p;
-            r.xs = Lv.n[0];
-            r.ys = Lv.n[1];
-            r.cap = Lv.n[0] + Lv.n[1] + 2;
-            if (slack[p]) {
-                r.bsum = reinterpret_cast<double*>(dev + at);
-                at += up256(((size_t)Lv.path_cap + 2) * band * sizeof(double));
-            }
+    for (int p = 0; p < n_pairs; p++) {
+        svxl_plane_pair(hp[p], lc.pair(p), summary + 4 * (size_t)p);
+        hp[p].slack = slack[p];
+        if (slack[p]) {
+            hp[p].bsum = reinterpret_cast<double*>(dev + at);
+            at += up256(((size_t)lc.pair(p).lev[0].path_cap + 2) * lc.band * sizeof(double));
         }
     }
-    rc = svxl_scratch_upload(ctx, (size_t)n_pairs * sizeof(SlackPair));
+    rc = svxl_scratch_upload(ctx, (size_t)n_pairs * sizeof(PlanePair));
     if (rc) return rc;
-    const SlackPair* dp = reinterpret_cast<const SlackPair*>(dev);
-    rc = launch_backward(ctx, dp, SlackPair{}, n_pairs, *types, band, 1);
+    const PlanePair* dp = reinterpret_cast<const PlanePair*>(dev);
+    rc = launch_backward(ctx, dp, PlanePair{}, n_pairs, *lc.types, lc.band, 1);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_path_slack, dim3(n_pairs), dim3(SK_THREADS), 0, ctx->stream, dp, SlackPair{}, 0, *types, band, 1);
+    hipLaunchKernelGGL(k_path_slack, dim3(n_pairs), dim3(SK_THREADS), 0, ctx->stream, dp, PlanePair{}, 0, *lc.types, lc.band, 1);
     SVX_LAUNCH_CHECK(ctx, "k_path_slack");
     return SVX_OK;
 }
