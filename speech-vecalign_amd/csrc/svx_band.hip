@@ -12,7 +12,8 @@
 //     other's k loop (the extra halo rows are L2 hits: neighbouring chunks run on the same XCD);
 //   * rows travel global -> LDS by LDS-DMA (global_load_lds_dwordx4, no VGPR stop-over, no ds_write) in 64-byte
 //     k-slabs = one MFMA k-step, into a ring of S stages: S - 1 slabs are in flight while one is multiplied, one
-//     workgroup barrier per slab, and the barrier does not drain the DMA queue (counted s_waitcnt vmcnt);
+//     workgroup barrier per slab, and the barrier does not drain the DMA queue (counted s_waitcnt vmcnt) -- the ring
+//     itself is SlabRing of svx_slab.h, shared with the tile sweep (svx_tiles.hip);
 //   * every DMA lane names its own 16 source bytes, so the LDS image is XOR-swizzled for free: the 16 lanes of
 //     each ds_read_b128 service group hit 16 different bank quads (no bank conflicts);
 //   * units = (alignment type, 16-row x tile), accumulators stay in registers over the whole k loop; tiles the
@@ -26,24 +27,17 @@
 #include <string.h>
 
 #include "svx_common.h"
+#include "svx_slab.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int B2_THREADS = 256;
 constexpr int B2_WAVES = 4;
 constexpr int B2_TB = 16;          // band cells per workgroup
-constexpr int B2_SLAB = 64;        // bytes of a row per k-slab
+constexpr int B2_SLAB = SLAB_BYTES;
 constexpr int B2_MAXPASS = 8;
 constexpr int B2_MAXSLOT = 20;     // overlap layers (both sides) one pass can stage
 constexpr int B2_MAXTPP = 16;      // alignment types per pass
-
-__device__ const uint4 band_zero16[4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
 
 // one pass = a run of consecutive alignment types and the overlap layers ("slots") they read
 struct BandPass {
@@ -55,38 +49,6 @@ struct BandPlan {
     int npass;
     BandPass pass[B2_MAXPASS];
 };
-
-__device__ __forceinline__ float cost_formula2(float sumx, int p, int q, float n0, float n1) {
-#pragma clang fp contract(off)
-    // dp_core.pyx:259-260, evaluated in double like the generated C, stored to float
-    return (float)((((2.0 * (double)p) * (double)q) * (1.0 - (double)sumx)) / ((1e-6 + (double)n0) + (double)n1));
-}
-
-// one k-slab (16 bytes per lane of A and of B) into a 16 x 16 accumulator tile
-template <typename E>
-__device__ __forceinline__ void mma_slab16(f32x4_t& acc, const uint4& a, const uint4& b);
-template <>
-__device__ __forceinline__ void mma_slab16<ElemBF16>(f32x4_t& acc, const uint4& a, const uint4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mma_slab16<ElemF16>(f32x4_t& acc, const uint4& a, const uint4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mma_slab16<ElemF32>(f32x4_t& acc, const uint4& a, const uint4& b) {
-    // lane (row r, group g) holds floats 4g .. 4g+3 of the 16-float slab; MFMA j multiplies element j of every
-    // lane: the four lanes of a row supply k = j, 4 + j, 8 + j, 12 + j -- A and B use the same map
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 struct Band2Args {
     const void* v0;  // [k0][n][d]
@@ -104,25 +66,15 @@ struct Band2Args {
     int* status;        // set to SVX_ERR_PATH when the path is not a unit-step lattice path
 };
 
-// LDS image of a stage: row r (slot * ROWS + loc) holds its 64-byte slab as four 16-byte pieces; piece kg sits at
-// 64 r + 16 (kg ^ h[(r >> 2) & 3]), h = {0, 2, 3, 1}: the 16 lanes of every ds_read_b128 service group (rows
-// {0-3, 12-15} of one k-group with rows {4-11} of the next) then cover all 16 bank quads.
-__device__ __forceinline__ int swz(int row_in_tile) { return (0x1320 >> (4 * ((row_in_tile >> 2) & 3))) & 3; }
-
 template <typename E, int ROWS, int NSLOT, int UPW, int S>
 struct Band2 {
+    using Ring = SlabRing<E, ROWS, NSLOT, B2_WAVES, S>;     // svx_slab.h: stage size, DMA pieces, the k loop
     static constexpr int XT = ROWS / 16;                    // 16-row tiles per side
-    static constexpr int STAGE = NSLOT * ROWS * B2_SLAB;    // bytes
-    static constexpr int NQ = NSLOT * ROWS / 16;            // 1-KiB DMA pieces per slab
-    static constexpr int PW = NQ / B2_WAVES;                // ... per wave
     static constexpr int TPP = B2_WAVES * UPW / XT;         // alignment types per pass
     static constexpr int TAMAX = 2 * (ROWS - 1) + 1;        // path points per chunk
     static constexpr int FS_FLOATS = (2 * (ROWS - B2_TB) + 1) * B2_TB * TPP;
-    static constexpr int KEL = B2_SLAB / (int)sizeof(typename E::storage);  // elements per slab
-    static_assert(NQ % B2_WAVES == 0, "DMA pieces must divide over the waves");
     static_assert(TPP <= B2_MAXTPP && NSLOT <= B2_MAXSLOT, "pass limits");
-    static_assert(S >= 2 && S <= 4, "ring depth");
-    static_assert(PW * (S - 2) <= 63, "vmcnt is a 6-bit counter");
+    static_assert(S <= 4, "BAND2_LDS declares four stages");
 };
 
 template <typename E, int ROWS, int NSLOT, int UPW, int S>
@@ -130,8 +82,9 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
                             char* st0, char* st1, char* st2, char* st3, float* Fs, int* spx, int* spy, float* snrm, float* sinv,
                             int* ltx, int* lty, int* tmask, int* lslot) {
     using C = Band2<E, ROWS, NSLOT, UPW, S>;
+    using R = typename C::Ring;
     using St = typename E::storage;
-    constexpr int XT = C::XT, PW = C::PW;
+    constexpr int XT = C::XT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // an SGPR: everything indexed by it stays scalar
     const int B = 2 * g.W, b0 = chunk_b * B2_TB;
@@ -139,7 +92,6 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
     const int esz = (int)sizeof(St);
     const int rowbytes = g.d * esz;
     const int NK = (rowbytes + B2_SLAB - 1) / B2_SLAB;
-    char* stages[4] = {st0, st1, st2, st3};
 
     // ---- the chunk's path points
     if (tid < TAe) {
@@ -166,6 +118,7 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
     // (a path that is not unit-step could ask for more rows than are staged: the status flag is already set, stay in bounds)
     NXn = NXn < 1 ? 1 : (NXn > ROWS ? ROWS : NXn);
     NYn = NYn < 1 ? 1 : (NYn > ROWS ? ROWS : NYn);
+    const SlabSide sx{g.v0, g.nrm0, g.inv0, X0, NXn, g.n}, sy{g.v1, g.nrm1, g.inv1, Y0, NYn, g.m};
     // tiles that hold band cells
     if (tid < TAe) {
         const int ya = spy[tid];
@@ -186,7 +139,6 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
     }
 
     const int lrow = lane & 15, lkg = lane >> 4;
-    const int loff = lrow * B2_SLAB + 16 * (lkg ^ swz(lrow));   // this lane's fragment inside a 16-row tile
 
     for (int pi = 0; pi < plan.npass; pi++) {
         const BandPass& ps = plan.pass[pi];
@@ -194,130 +146,21 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
         // the pass's slot table -> LDS (one round trip to the kernel-argument segment instead of one per use)
         if (tid < NSLOT) lslot[tid] = tid < nslot ? ps.slot_info[tid] : 0;
         __syncthreads();  // slot table and tile masks complete / the previous pass is done with the stages and Fs
-        // ---- per-row scalars of this pass (needed in the epilogue only: the loads ride out the k loop in registers)
-        constexpr int SPT = (NSLOT * ROWS + B2_THREADS - 1) / B2_THREADS;
-        float r_nrm[SPT], r_inv[SPT];
-#pragma unroll
-        for (int i = 0; i < SPT; i++) {
-            const int r = tid + i * B2_THREADS;
-            r_nrm[i] = 0.f;
-            r_inv[i] = 1.f;
-            if (r < nslot * ROWS) {
-                const int slot = r / ROWS, loc = r % ROWS;
-                const int side = lslot[slot] >> 8, layer = lslot[slot] & 255;
-                const int gi = (side ? Y0 : X0) + loc, nn = side ? g.m : g.n;
-                if (loc < (side ? NYn : NXn) && gi >= 0 && gi < nn) {
-                    const size_t o = (size_t)layer * nn + gi;
-                    r_nrm[i] = (side ? g.nrm1 : g.nrm0)[o];
-                    const float* iv = side ? g.inv1 : g.inv0;
-                    if (iv) r_inv[i] = iv[o];
-                }
-            }
-        }
-        // ---- this lane's DMA sources: piece q = wave + 4 i covers rows 16 q .. 16 q + 15, lane -> (row, 16-byte piece)
-        const char* src[PW];
-        unsigned live = 0;
-#pragma unroll
-        for (int i = 0; i < PW; i++) {
-            const int q = wave + B2_WAVES * i;
-            const int r = 16 * q + (lane >> 2);
-            const int slot = r / ROWS, loc = r % ROWS;
-            const int piece = (lane & 3) ^ swz(lane >> 2);
-            src[i] = reinterpret_cast<const char*>(band_zero16);
-            if (slot < nslot) {
-                const int side = lslot[slot] >> 8, layer = lslot[slot] & 255;
-                const int gi = (side ? Y0 : X0) + loc, nn = side ? g.m : g.n;
-                if (loc < (side ? NYn : NXn) && gi >= 0 && gi < nn) {
-                    src[i] = reinterpret_cast<const char*>(side ? g.v1 : g.v0) + ((size_t)layer * nn + gi) * rowbytes + piece * 16;
-                    live |= 1u << i;
-                }
-            }
-        }
-        const int piece_byte = ((lane & 3) ^ swz(lane >> 2)) * 16;
-        auto issue = [&](int k, char* stage) {
-#pragma unroll
-            for (int i = 0; i < PW; i++) {
-                const char* s = src[i] + (size_t)k * B2_SLAB;
-                if (!((live >> i) & 1u) || k * B2_SLAB + piece_byte >= rowbytes) s = reinterpret_cast<const char*>(band_zero16);
-                __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(stage + (wave + B2_WAVES * i) * 1024), 16, 0, 0);
-            }
-        };
-        // ---- units of this wave: (type of the pass, x tile); every unit multiplies its x tile with all XT y tiles
-        // (with two tiles per side the band touches all four; the unused corner of a larger staging area is masked)
+        // ---- the ring of svx_slab.h over this pass's slots: per-row scalars (epilogue only: they ride out the k loop in
+        // registers), DMA sources, this wave's units (type of the pass, x tile), then the k loop
+        auto slot_of = [&](int slot) { return slot < nslot ? SlabSlot{lslot[slot] >> 8, lslot[slot] & 255} : SlabSlot{-1, 0}; };
+        auto type_slots = [&](int tl) { return SlabPair{ps.type_slots[tl] & 255, ps.type_slots[tl] >> 8}; };
+        float r_nrm[R::SPT], r_inv[R::SPT];
+        R::row_scalars(slot_of, sx, sy, tid, r_nrm, r_inv);
+        typename R::Src src;
+        R::sources(slot_of, sx, sy, rowbytes, wave, lane, src);
         f32x4_t acc[UPW][XT];
-        int aoff[UPW], boffb[UPW], umask[UPW];
+        typename R::template Units<UPW> un;
         const int nunits = ntp * XT;
-#pragma unroll
-        for (int s = 0; s < UPW; s++) {
-#pragma unroll
-            for (int j = 0; j < XT; j++) acc[s][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-            const int u = wave + B2_WAVES * s;
-            const int tl = u < nunits ? u / XT : 0, xt = u % XT;
-            const int tsl = ps.type_slots[tl];
-            aoff[s] = ((tsl & 255) * ROWS + xt * 16) * B2_SLAB + loff;
-            boffb[s] = ((tsl >> 8) * ROWS) * B2_SLAB + loff;
-            umask[s] = u < nunits ? (XT <= 2 ? (1 << XT) - 1 : __builtin_amdgcn_readfirstlane(tmask[xt])) : 0;
-        }
-        auto mma = [&](const char* stage) {
-            uint4 fa[UPW], fb[UPW][XT];
-#pragma unroll
-            for (int s = 0; s < UPW; s++) {
-                if (umask[s]) {  // scalar
-                    fa[s] = *reinterpret_cast<const uint4*>(stage + aoff[s]);
-#pragma unroll
-                    for (int j = 0; j < XT; j++)
-                        if (XT <= 2 || ((umask[s] >> j) & 1)) fb[s][j] = *reinterpret_cast<const uint4*>(stage + boffb[s] + j * 16 * B2_SLAB);
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < UPW; s++) {
-                if (umask[s]) {
-#pragma unroll
-                    for (int j = 0; j < XT; j++)
-                        if (XT <= 2 || ((umask[s] >> j) & 1)) mma_slab16<E>(acc[s][j], fa[s], fb[s][j]);
-                }
-            }
-        };
-        // ---- k loop: slab k is multiplied out of stage k % S while slabs k+1 .. k+S-2 are in flight
-#pragma unroll
-        for (int k = 0; k < S - 1; k++)
-            if (k < NK) issue(k, stages[k]);
-        auto step = [&](int k, const char* rd, char* wr) {
-            if (k < NK) {
-                const int younger = (NK - 1 - k) < (S - 2) ? (NK - 1 - k) : (S - 2);  // slabs issued after slab k
-                if (younger >= 2) wait_vm<2 * PW>();
-                else if (younger == 1) wait_vm<PW>();
-                else wait_vm<0>();
-                __builtin_amdgcn_s_barrier();   // every wave's pieces of slab k have landed; stage (k-1) % S is free
-                asm volatile("" ::: "memory");
-                if (k + S - 1 < NK) issue(k + S - 1, wr);
-                mma(rd);
-            }
-        };
-        for (int k0 = 0; k0 < NK; k0 += S) {
-            if (S == 2) {
-                step(k0, st0, st1);
-                step(k0 + 1, st1, st0);
-            } else if (S == 3) {
-                step(k0, st0, st2);
-                step(k0 + 1, st1, st0);
-                step(k0 + 2, st2, st1);
-            } else {
-                step(k0, st0, st3);
-                step(k0 + 1, st1, st0);
-                step(k0 + 2, st2, st1);
-                step(k0 + 3, st3, st2);
-            }
-        }
+        R::template units<UPW, XT>(type_slots, nunits, tmask, wave, lane, un, acc);
+        R::template run<UPW, XT>(NK, src, un, acc, st0, st1, st2, st3, nullptr);
         // ---- epilogue
-#pragma unroll
-        for (int i = 0; i < SPT; i++) {
-            const int r = tid + i * B2_THREADS;
-            if (r < NSLOT * ROWS) {
-                snrm[r] = r_nrm[i];
-                sinv[r] = r_inv[i];
-            }
-        }
+        R::store_scalars(snrm, sinv, tid, r_nrm, r_inv);
         __syncthreads();
         const float inf = __builtin_inff();
 #pragma unroll
@@ -329,7 +172,7 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
             const int xs = (ps.type_slots[tl] & 255) * ROWS, ys = (ps.type_slots[tl] >> 8) * ROWS;
 #pragma unroll
             for (int j = 0; j < XT; j++) {
-                if (!((umask[s] >> j) & 1)) continue;
+                if (!((un.umask[s] >> j) & 1)) continue;
                 const int yloc = 16 * j + lrow, yy = Y0 + yloc;
                 const float ny = snrm[ys + yloc], iy = sinv[ys + yloc];
 #pragma unroll
@@ -342,7 +185,7 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
                     float c = inf;
                     if (xx >= 0 && xx < g.n && yy >= 0 && yy < g.m) {
                         const float sumx = acc[s][j][r] * sinv[xs + xloc] * iy;
-                        c = cost_formula2(sumx, p, q, snrm[xs + xloc], ny);
+                        c = cost_formula(sumx, p, q, snrm[xs + xloc], ny);
                     }
                     Fs[(ai * ntp + tl) * TBe + bi] = c;
                 }
@@ -371,10 +214,10 @@ __device__ void band2_block(const Band2Args& g, const SvxTypes& ty, const BandPl
 // the ds_reads of one stage never touch a stage an LDS-DMA is still filling, and does not drain the DMA queue in front
 // of them.
 #define BAND2_LDS(C, ROWS, NSLOT, S)                                           \
-    __shared__ __attribute__((aligned(1024))) char st0[C::STAGE];              \
-    __shared__ __attribute__((aligned(1024))) char st1[C::STAGE];              \
-    __shared__ __attribute__((aligned(1024))) char st2[S >= 3 ? C::STAGE : 16]; \
-    __shared__ __attribute__((aligned(1024))) char st3[S >= 4 ? C::STAGE : 16]; \
+    __shared__ __attribute__((aligned(1024))) char st0[C::Ring::STAGE];              \
+    __shared__ __attribute__((aligned(1024))) char st1[C::Ring::STAGE];              \
+    __shared__ __attribute__((aligned(1024))) char st2[S >= 3 ? C::Ring::STAGE : 16]; \
+    __shared__ __attribute__((aligned(1024))) char st3[S >= 4 ? C::Ring::STAGE : 16]; \
     __shared__ __attribute__((aligned(16))) float Fs[C::FS_FLOATS];            \
     __shared__ int spx[C::TAMAX + 1], spy[C::TAMAX + 1];                       \
     __shared__ float snrm[NSLOT * ROWS], sinv[NSLOT * ROWS];                   \
@@ -509,22 +352,22 @@ __device__ void band3_block(const Band2Args& g, const BandPlan3& plan, int a0, i
         }
     }
     const int lrow = lane & 15, lkg = lane >> 4;
-    const int loff = lrow * B2_SLAB + 16 * (lkg ^ swz(lrow));
+    const int loff = lrow * B2_SLAB + 16 * (lkg ^ slab_swz(lrow));
     // ---- this wave's DMA piece of a target slab (rows 16 wave .. 16 wave + 15 of the stage) and its own source rows
-    const char* ysrc = reinterpret_cast<const char*>(band_zero16);
+    const char* ysrc = reinterpret_cast<const char*>(slab_zero16);
     bool ylive = false;
     {
         const int r = 16 * wave + (lane >> 2), yl = r / ROWS, loc = r % ROWS;
         const int gi = Y0 + loc;
         if (yl < ky && loc < NYn && gi >= 0 && gi < g.m) {
-            ysrc = reinterpret_cast<const char*>(g.v1) + ((size_t)yl * g.m + gi) * rowbytes + ((lane & 3) ^ swz(lane >> 2)) * 16;
+            ysrc = reinterpret_cast<const char*>(g.v1) + ((size_t)yl * g.m + gi) * rowbytes + ((lane & 3) ^ slab_swz(lane >> 2)) * 16;
             ylive = true;
         }
     }
     // (address-space-1 pointers throughout: a generic pointer would make these flat loads, which the compiler orders
     //  against every pending LDS-DMA with s_waitcnt vmcnt(0))
     typedef const __attribute__((address_space(1))) char* gcp_t;
-    const gcp_t zsrc = (gcp_t)(gptr_t) reinterpret_cast<const char*>(band_zero16);
+    const gcp_t zsrc = (gcp_t)(gptr_t) reinterpret_cast<const char*>(slab_zero16);
     gcp_t xsrc = zsrc;
     bool xlive = false;
     {
@@ -535,7 +378,7 @@ __device__ void band3_block(const Band2Args& g, const BandPlan3& plan, int a0, i
         }
     }
     auto issue_y = [&](int k, char* stage) {
-        const char* s2 = ylive ? ysrc + (size_t)k * B2_SLAB : reinterpret_cast<const char*>(band_zero16);
+        const char* s2 = ylive ? ysrc + (size_t)k * B2_SLAB : reinterpret_cast<const char*>(slab_zero16);
         __builtin_amdgcn_global_load_lds((gptr_t)s2, (lptr_t)(stage + wave * 1024), 16, 0, 0);
     };
     auto load_x = [&](int k) -> uint4 {
@@ -673,7 +516,7 @@ __device__ void band3_block(const Band2Args& g, const BandPlan3& plan, int a0, i
                 float c = inf;
                 if (xx >= 0 && xx < g.n && yy >= 0 && yy < g.m) {
                     const float sumx = acc[i][j][r] * sinv[xs + xloc] * iy;
-                    c = cost_formula2(sumx, p, q, snrm[xs + xloc], ny);
+                    c = cost_formula(sumx, p, q, snrm[xs + xloc], ny);
                 }
                 Fs[(ai * T + t) * TBe + bi] = c;
             }

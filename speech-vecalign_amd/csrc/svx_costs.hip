@@ -12,12 +12,9 @@
 #include <stdlib.h>
 
 #include "svx_common.h"
+#include "svx_slab.h"   // the vector typedefs and cost_formula
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 constexpr int RS = 144;        // LDS row stride in bytes: 128-byte k-slab + 16 pad (conflict-free b128 reads)
 
@@ -71,12 +68,6 @@ __device__ __forceinline__ void stage_slab(char* slab, const char* const* rowptr
         if (ptr != nullptr && kel < d) v = *reinterpret_cast<const uint4*>(ptr + (size_t)kel * sizeof(S));
         *reinterpret_cast<uint4*>(slab + r * RS + p * 16) = v;
     }
-}
-
-__device__ __forceinline__ float cost_formula(float sumx, int p, int q, float n0, float n1) {
-#pragma clang fp contract(off)
-    // dp_core.pyx:259-260, evaluated in double like the generated C, stored to float
-    return (float)((((2.0 * (double)p) * (double)q) * (1.0 - (double)sumx)) / ((1e-6 + (double)n0) + (double)n1));
 }
 
 // ------------------------------------------------------------------------------ dense costs

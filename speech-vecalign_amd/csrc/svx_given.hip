@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "svx_common.h"
+#include "svx_slab.h"   // cost_formula: the level-0 band-cost kernel's expression
 
 #define SVX_GV_CHUNK 256
 #define SVX_GV_STEP 4   // 16-byte pieces per lane and side in flight
@@ -69,12 +70,6 @@ __device__ __forceinline__ bool node_outside(const GivenPair& P, long long x, lo
     if (a >= a_out) return true;
     const long long b = y - (long long)gld(P.boff_out + a);
     return b < 0 || b >= B;
-}
-
-__device__ __forceinline__ float given_cost(float sumx, int p, int q, float n0, float n1) {
-#pragma clang fp contract(off)
-    // the level-0 band-cost kernel's expression (dp_core.pyx:259-260): double, stored to float
-    return (float)((((2.0 * (double)p) * (double)q) * (1.0 - (double)sumx)) / ((1e-6 + (double)n0) + (double)n1));
 }
 
 // <x, y> of two candidate rows of `pieces` 16-byte pieces each, by one wave: lane l holds pieces l, l + 64, ...
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(SVX_GV_CHUNK) void k_given_rows(const GivenPair* __
         const size_t xrow = (size_t)(a.y - 1) * P.n + a.x + a.y - 1, yrow = (size_t)(a.w - 1) * P.m + a.z + a.w - 1;
         const float dot = wave_dot<E>(reinterpret_cast<const S*>(P.v[0]) + xrow * d, reinterpret_cast<const S*>(P.v[1]) + yrow * d, pieces, lane);
         const float sumx = dot * gld(P.inv[0] + xrow) * gld(P.inv[1] + yrow);
-        const float cj = given_cost(sumx, a.y, a.w, gld(P.nrm[0] + xrow), gld(P.nrm[1] + yrow));
+        const float cj = cost_formula(sumx, a.y, a.w, gld(P.nrm[0] + xrow), gld(P.nrm[1] + yrow));
         if (lane == j) cost = cj;
     }
     if (have && P.scores) {

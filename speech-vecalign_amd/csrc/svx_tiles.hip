@@ -10,7 +10,7 @@
 //
 // Here the lattice of DP nodes (x, y) is cut into 32 x 32 tiles.  A tile's T cost planes are 16 x 16 MFMA blocks
 // of the raw 16-bit / fp32 rows (32 rows x all overlap layers per side, LDS-DMA ring of swizzled 64-byte k-slabs:
-// the machinery of svx_band.hip), scaled by the two inverse norms and turned into costs in double like the
+// SlabRing of svx_slab.h, shared with svx_band.hip), scaled by the two inverse norms and turned into costs in double like the
 // reference; they never leave LDS.  The tile's nodes are then relaxed along its 63 anti-diagonals by one wave
 // (two half-waves split the moves and merge by (total, move) so that the reference's "first strictly smaller
 // candidate" order is kept), reading a 4..8 node halo of the float64 sums of the tiles above and to the left.
@@ -26,56 +26,20 @@
 #include <string.h>
 
 #include "svx_common.h"
+#include "svx_slab.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int TL = 32;             // tile side in DP nodes
-constexpr int TT_THREADS = 256, TT_WAVES = 4, TT_SLAB = 64;
+constexpr int TT_THREADS = 256, TT_WAVES = 4, TT_SLAB = SLAB_BYTES;
 constexpr int TT_MAXSLOT = 12, TT_MAXT = 16, TT_HALO = 8;
 constexpr int CS_W = TL + TT_HALO;  // csum tile with halo
-
-__device__ const uint4 tile_zero16[4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
 
 struct TilePlan {
     int nt, nslot, halo;
     int slot_info[TT_MAXSLOT];  // side << 8 | layer
     int type_slots[TT_MAXT];    // x slot | y slot << 8
 };
-
-__device__ __forceinline__ float cost_formula_t(float sumx, int p, int q, float n0, float n1) {
-#pragma clang fp contract(off)
-    return (float)((((2.0 * (double)p) * (double)q) * (1.0 - (double)sumx)) / ((1e-6 + (double)n0) + (double)n1));
-}
-
-template <typename E>
-__device__ __forceinline__ void mma_t16(f32x4_t& acc, const uint4& a, const uint4& b);
-template <>
-__device__ __forceinline__ void mma_t16<ElemBF16>(f32x4_t& acc, const uint4& a, const uint4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mma_t16<ElemF16>(f32x4_t& acc, const uint4& a, const uint4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mma_t16<ElemF32>(f32x4_t& acc, const uint4& a, const uint4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm_t() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ int swz_t(int row_in_tile) { return (0x1320 >> (4 * ((row_in_tile >> 2) & 3))) & 3; }
 
 // b_offset_out of a pair, then per tile anti-diagonal s the run of tiles (I, s - I) that hold band nodes.  Everything
 // comes from the level's search path: the straight line, or the path of a prior (SVX_SEARCH_AROUND_WIDE).  The run is
@@ -167,13 +131,72 @@ __global__ __launch_bounds__(1024) void k_tile_prefix(const SvxPairDev* __restri
 
 template <typename E, int NSLOT, int UPW, int S>
 struct TileCfg {
-    static constexpr int STAGE = NSLOT * TL * TT_SLAB;
-    static constexpr int NQ = NSLOT * TL / 16;
-    static constexpr int PW = NQ / TT_WAVES;
+    using Ring = SlabRing<E, TL, NSLOT, TT_WAVES, S>;   // svx_slab.h: stage size, DMA pieces, the k loop
     static constexpr int TPP = TT_WAVES * UPW / 2;
-    static_assert(NQ % TT_WAVES == 0, "DMA pieces must divide over the waves");
     static_assert(TPP <= TT_MAXT && NSLOT <= TT_MAXSLOT, "plan limits");
 };
+
+// (diagnostic build-in: with SVX_TILE_PROF=1 thread 0 sums the 100 MHz ticks of every phase into prof[0..6])
+struct TileStamp {
+    unsigned long long* prof;
+    unsigned long long t_prev;
+    __device__ __forceinline__ explicit TileStamp(unsigned long long* p) : prof(p), t_prev(p ? __builtin_amdgcn_s_memrealtime() : 0) {}
+    __device__ __forceinline__ void operator()(int slot) {
+        if (prof && threadIdx.x == 0) {
+            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+            atomicAdd(prof + slot, now - t_prev);
+            t_prev = now;
+        }
+    }
+};
+
+// The (diagonal, pair) entry of ticket tk: the last e with gpref[e] <= tk, searched forward from the workgroup's previous
+// entry (tickets grow).  Gallop, then bisect: a workgroup's next ticket is usually a few entries ahead.
+__device__ __forceinline__ long long tile_entry(const int* __restrict__ gpref, long long nent, int tk, long long ecur) {
+    if (gpref[ecur + 1] <= tk) {
+        long long step = 1, lo = ecur + 1, hi = nent - 1;
+        while (lo + step < nent && gpref[lo + step] <= tk) { lo += step; step <<= 1; }
+        if (lo + step < hi) hi = lo + step;
+        while (lo < hi) {
+            const long long mid = (lo + hi + 1) >> 1;
+            if (gpref[mid] <= tk) lo = mid; else hi = mid - 1;
+        }
+        ecur = lo;
+    }
+    return ecur;
+}
+
+// The cost planes of a wave's units: accumulators x the two inverse norms -> costs in double like the reference.
+// plane_of(type of the pass) names the type's sizes, the first staged rows of its two slots and where the plane goes:
+// cell (x row, y row) at dst[(x * TL + y) * YS] -- YS = 1: the LDS planes of k_band_tiles, 8: k_band_tiles_gen's
+// slice of global scratch.
+struct TilePlane {
+    int p, q, xsl, ysl;
+    float* dst;
+};
+template <int UPW, int YS, class PlaneOf>
+__device__ __forceinline__ void tile_cost_planes(const f32x4_t (&acc)[UPW][2], int nunits, int wave, int lane, const float* snrm,
+                                                 const float* sinv, PlaneOf plane_of) {
+    const int lrow = lane & 15, lkg = lane >> 4;
+#pragma unroll
+    for (int u2 = 0; u2 < UPW; u2++) {
+        const int u = wave + TT_WAVES * u2;
+        if (u >= nunits) continue;
+        const int xt = u % 2;
+        const TilePlane tp = plane_of(u / 2);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int yloc = 16 * j + lrow;
+            const float ny = snrm[tp.ysl + yloc], iy = sinv[tp.ysl + yloc];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int xloc = 16 * xt + 4 * lkg + r;
+                const float sumx = acc[u2][j][r] * sinv[tp.xsl + xloc] * iy;
+                tp.dst[(xloc * TL + yloc) * YS] = cost_formula(sumx, tp.p, tp.q, snrm[tp.xsl + xloc], ny);
+            }
+        }
+    }
+}
 
 struct DpMerge {
     double tot;
@@ -186,12 +209,12 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
                                                            unsigned long long* prof) {
     using C = TileCfg<E, NSLOT, UPW, S>;
     using St = typename E::storage;
-    constexpr int PW = C::PW;
-    __shared__ __attribute__((aligned(1024))) char st0[C::STAGE];
-    __shared__ __attribute__((aligned(1024))) char st1[C::STAGE];
-    __shared__ __attribute__((aligned(1024))) char st2[S >= 3 ? C::STAGE : 16];
-    __shared__ __attribute__((aligned(1024))) char st3[S >= 4 ? C::STAGE : 16];
-    __shared__ __attribute__((aligned(1024))) char st4[S >= 5 ? C::STAGE : 16];
+    using R = typename C::Ring;
+    __shared__ __attribute__((aligned(1024))) char st0[R::STAGE];
+    __shared__ __attribute__((aligned(1024))) char st1[R::STAGE];
+    __shared__ __attribute__((aligned(1024))) char st2[S >= 3 ? R::STAGE : 16];
+    __shared__ __attribute__((aligned(1024))) char st3[S >= 4 ? R::STAGE : 16];
+    __shared__ __attribute__((aligned(1024))) char st4[S >= 5 ? R::STAGE : 16];
     __shared__ __attribute__((aligned(16))) float planes[C::TPP * TL * TL];   // [type][x row][y row] costs of the tile
     __shared__ __attribute__((aligned(16))) double cs[CS_W * CS_W + 2];       // csum of the tile's nodes and halo; [CS_W^2] = +inf
     __shared__ unsigned char bpt[TL * TL];
@@ -205,20 +228,10 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
     const long long nent = (long long)max_nd * n_pairs;
     const int total = gpref[nent];
     for (int t = tid; t < NTt; t += TT_THREADS) tpk[t] = (int)ty.x[t] | ((int)ty.y[t] << 8);
-    const int lrow = lane & 15, lkg = lane >> 4;
-    const int loff = lrow * TT_SLAB + 16 * (lkg ^ swz_t(lrow));
     const double inf = __builtin_inf();
     long long ecur = 0;  // tickets grow: the (diagonal, pair) entry of a workgroup's ticket only moves forward
 
-    // (diagnostic build-in: with SVX_TILE_PROF=1 thread 0 sums the 100 MHz ticks of every phase into prof[0..6])
-    unsigned long long t_prev = prof ? __builtin_amdgcn_s_memrealtime() : 0;
-    auto stamp = [&](int slot) {
-        if (prof && tid == 0) {
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            atomicAdd(prof + slot, now - t_prev);
-            t_prev = now;
-        }
-    };
+    TileStamp stamp(prof);
     for (;;) {
         __syncthreads();  // the previous tile is finished with LDS
         stamp(6);
@@ -226,17 +239,7 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
         __syncthreads();
         const int tk = sh_ticket;
         if (tk >= total) break;
-        // (gallop, then bisect: a workgroup's next ticket is usually a few entries ahead)
-        if (gpref[ecur + 1] <= tk) {
-            long long step = 1, lo = ecur + 1, hi = nent - 1;
-            while (lo + step < nent && gpref[lo + step] <= tk) { lo += step; step <<= 1; }
-            if (lo + step < hi) hi = lo + step;
-            while (lo < hi) {
-                const long long mid = (lo + hi + 1) >> 1;
-                if (gpref[mid] <= tk) lo = mid; else hi = mid - 1;
-            }
-            ecur = lo;
-        }
+        ecur = tile_entry(gpref, nent, tk, ecur);
         const int s = (int)(ecur / n_pairs);
         const SvxPairDev& P = pairs[ecur % n_pairs];
         const SvxLevel& Lv = P.lev[0];
@@ -250,126 +253,23 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
 
         stamp(0);
         // ---- phase 1: cost planes (no neighbour needed)
-        constexpr int SPT = (NSLOT * TL + TT_THREADS - 1) / TT_THREADS;
-        float r_nrm[SPT], r_inv[SPT];
-#pragma unroll
-        for (int i = 0; i < SPT; i++) {
-            const int r = tid + i * TT_THREADS;
-            r_nrm[i] = 0.f;
-            r_inv[i] = 1.f;
-            if (r < plan.nslot * TL) {
-                const int slot = r / TL, loc = r % TL;
-                const int side = plan.slot_info[slot] >> 8, layer = plan.slot_info[slot] & 255;
-                const int gi = (side ? Y0 : X0) + loc, nn = side ? ys : xs;
-                if (gi >= 0 && gi < nn) {
-                    const size_t o = (size_t)layer * nn + gi;
-                    r_nrm[i] = Lv.nrm[side][o];
-                    if (Lv.inv[side]) r_inv[i] = Lv.inv[side][o];
-                }
-            }
-        }
-        const char* src[PW];
-        unsigned live = 0;
-#pragma unroll
-        for (int i = 0; i < PW; i++) {
-            const int q = wave + TT_WAVES * i;
-            const int r = 16 * q + (lane >> 2);
-            const int slot = r / TL, loc = r % TL;
-            const int piece = (lane & 3) ^ swz_t(lane >> 2);
-            src[i] = reinterpret_cast<const char*>(tile_zero16);
-            if (slot < plan.nslot) {
-                const int side = plan.slot_info[slot] >> 8, layer = plan.slot_info[slot] & 255;
-                const int gi = (side ? Y0 : X0) + loc, nn = side ? ys : xs;
-                if (gi >= 0 && gi < nn) {
-                    src[i] = reinterpret_cast<const char*>(P.v[side]) + ((size_t)layer * nn + gi) * rowbytes + piece * 16;
-                    live |= 1u << i;
-                }
-            }
-        }
-        const int piece_byte = ((lane & 3) ^ swz_t(lane >> 2)) * 16;
-        auto issue = [&](int k, char* stage) {
-#pragma unroll
-            for (int i = 0; i < PW; i++) {
-                const char* s2 = src[i] + (size_t)k * TT_SLAB;
-                if (!((live >> i) & 1u) || k * TT_SLAB + piece_byte >= rowbytes) s2 = reinterpret_cast<const char*>(tile_zero16);
-                __builtin_amdgcn_global_load_lds((gptr_t)s2, (lptr_t)(stage + (wave + TT_WAVES * i) * 1024), 16, 0, 0);
-            }
+        // (the ring of svx_slab.h over the plan's slots: per-row scalars in registers across the k loop, DMA sources, this
+        //  wave's units (type, x tile of the two), the k loop)
+        const SlabSide sx{P.v[0], Lv.nrm[0], Lv.inv[0], X0, TL, xs}, sy{P.v[1], Lv.nrm[1], Lv.inv[1], Y0, TL, ys};
+        auto slot_of = [&](int slot) {
+            return slot < plan.nslot ? SlabSlot{plan.slot_info[slot] >> 8, plan.slot_info[slot] & 255} : SlabSlot{-1, 0};
         };
+        auto type_slots = [&](int tl) { return SlabPair{plan.type_slots[tl] & 255, plan.type_slots[tl] >> 8}; };
+        float r_nrm[R::SPT], r_inv[R::SPT];
+        R::row_scalars(slot_of, sx, sy, tid, r_nrm, r_inv);
+        typename R::Src src;
+        R::sources(slot_of, sx, sy, rowbytes, wave, lane, src);
         f32x4_t acc[UPW][2];
-        int aoff[UPW], boffb[UPW];
+        typename R::template Units<UPW> un;
         const int nunits = T * 2;
-#pragma unroll
-        for (int u2 = 0; u2 < UPW; u2++) {
-            acc[u2][0] = acc[u2][1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-            const int u = wave + TT_WAVES * u2;
-            const int tl = u < nunits ? u / 2 : 0, xt = u % 2;
-            const int tsl = plan.type_slots[tl];
-            aoff[u2] = ((tsl & 255) * TL + xt * 16) * TT_SLAB + loff;
-            boffb[u2] = ((tsl >> 8) * TL) * TT_SLAB + loff;
-        }
-        auto mma = [&](const char* stage) {
-            uint4 fa[UPW], fb[UPW][2];
-#pragma unroll
-            for (int u2 = 0; u2 < UPW; u2++)
-                if (wave + TT_WAVES * u2 < nunits) {
-                    fa[u2] = *reinterpret_cast<const uint4*>(stage + aoff[u2]);
-                    fb[u2][0] = *reinterpret_cast<const uint4*>(stage + boffb[u2]);
-                    fb[u2][1] = *reinterpret_cast<const uint4*>(stage + boffb[u2] + 16 * TT_SLAB);
-                }
-#pragma unroll
-            for (int u2 = 0; u2 < UPW; u2++)
-                if (wave + TT_WAVES * u2 < nunits) {
-                    mma_t16<E>(acc[u2][0], fa[u2], fb[u2][0]);
-                    mma_t16<E>(acc[u2][1], fa[u2], fb[u2][1]);
-                }
-        };
-        char* stages[5] = {st0, st1, st2, st3, st4};
-        static_assert(S >= 2 && S <= 5 && 3 * PW <= 63, "ring depth / vmcnt range");
-#pragma unroll
-        for (int k = 0; k < S - 1; k++)
-            if (k < NK) issue(k, stages[k]);
-        auto step = [&](int k, const char* rd, char* wr) {
-            if (k < NK) {
-                const int younger = (NK - 1 - k) < (S - 2) ? (NK - 1 - k) : (S - 2);  // slabs issued after slab k
-                if (younger >= 3) wait_vm_t<3 * PW>();
-                else if (younger == 2) wait_vm_t<2 * PW>();
-                else if (younger == 1) wait_vm_t<PW>();
-                else wait_vm_t<0>();
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                if (k + S - 1 < NK) issue(k + S - 1, wr);
-                mma(rd);
-            }
-        };
-        for (int k0 = 0; k0 < NK; k0 += S) {
-            if (S == 2) {
-                step(k0, st0, st1);
-                step(k0 + 1, st1, st0);
-            } else if (S == 3) {
-                step(k0, st0, st2);
-                step(k0 + 1, st1, st0);
-                step(k0 + 2, st2, st1);
-            } else if (S == 4) {
-                step(k0, st0, st3);
-                step(k0 + 1, st1, st0);
-                step(k0 + 2, st2, st1);
-                step(k0 + 3, st3, st2);
-            } else {
-                step(k0, st0, st4);
-                step(k0 + 1, st1, st0);
-                step(k0 + 2, st2, st1);
-                step(k0 + 3, st3, st2);
-                step(k0 + 4, st4, st3);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SPT; i++) {
-            const int r = tid + i * TT_THREADS;
-            if (r < NSLOT * TL) {
-                snrm[r] = r_nrm[i];
-                sinv[r] = r_inv[i];
-            }
-        }
+        R::template units<UPW, 2>(type_slots, nunits, nullptr, wave, lane, un, acc);
+        R::template run<UPW, 2>(NK, src, un, acc, st0, st1, st2, st3, st4);
+        R::store_scalars(snrm, sinv, tid, r_nrm, r_inv);
         // band offsets of the node diagonals this tile and its halo touch: a in [32 s - 2 H, 32 s + 62]
         const int abase = TL * s - 2 * H;
         for (int i = tid; i < 2 * TL + 2 * H; i += TT_THREADS) {
@@ -377,25 +277,9 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
             bo_l[i] = (a >= 0 && a < A + 2) ? Lv.boff_out[a] : (1 << 28);  // (no such diagonal: nothing is in its band)
         }
         __syncthreads();
-#pragma unroll
-        for (int u2 = 0; u2 < UPW; u2++) {
-            const int u = wave + TT_WAVES * u2;
-            if (u >= nunits) continue;
-            const int tl = u / 2, xt = u % 2;
-            const int p = tpk[tl] & 255, q = tpk[tl] >> 8;
-            const int xsl = (plan.type_slots[tl] & 255) * TL, ysl = (plan.type_slots[tl] >> 8) * TL;
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const int yloc = 16 * j + lrow;
-                const float ny = snrm[ysl + yloc], iy = sinv[ysl + yloc];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int xloc = 16 * xt + 4 * lkg + r;
-                    const float sumx = acc[u2][j][r] * sinv[xsl + xloc] * iy;
-                    planes[(tl * TL + xloc) * TL + yloc] = cost_formula_t(sumx, p, q, snrm[xsl + xloc], ny);
-                }
-            }
-        }
+        tile_cost_planes<UPW, 1>(acc, nunits, wave, lane, snrm, sinv, [&](int tl) {
+            return TilePlane{tpk[tl] & 255, tpk[tl] >> 8, (plan.type_slots[tl] & 255) * TL, (plan.type_slots[tl] >> 8) * TL, planes + tl * TL * TL};
+        });
         stamp(1);
         // ---- phase 2: wait for the neighbours (all three, when they exist, have smaller tickets), then their halo
         if (tid == 0) {
@@ -614,10 +498,10 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_gen(const SvxPairDev*
                                                                unsigned long long* prof) {
     using C = TileCfg<E, TG_NSLOT, TG_UPW, TG_S>;
     using St = typename E::storage;
-    constexpr int PW = C::PW;
-    constexpr int RING = TG_S * C::STAGE;
+    using R = typename C::Ring;
+    constexpr int RING = TG_S * R::STAGE;
     constexpr int LDS_MAIN = (RING > TG_CSMAX * 8 ? RING : TG_CSMAX * 8);
-    constexpr int STG = BIGH ? 16 : C::STAGE;
+    constexpr int STG = BIGH ? 16 : R::STAGE;
     __shared__ __attribute__((aligned(1024))) char st0[STG];
     __shared__ __attribute__((aligned(1024))) char st1[STG];
     __shared__ __attribute__((aligned(1024))) char st2[STG];
@@ -638,19 +522,10 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_gen(const SvxPairDev*
     const long long nent = (long long)max_nd * n_pairs;
     const int total = gpref[nent];
     for (int t = tid; t < NTt; t += TT_THREADS) tpk[t] = (int)ty.x[t] | ((int)ty.y[t] << 8);
-    const int lrow = lane & 15, lkg = lane >> 4;
-    const int loff = lrow * TT_SLAB + 16 * (lkg ^ swz_t(lrow));
     const double inf = __builtin_inf();
     long long ecur = 0;
 
-    unsigned long long t_prev = prof ? __builtin_amdgcn_s_memrealtime() : 0;
-    auto stamp = [&](int slot) {
-        if (prof && tid == 0) {
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            atomicAdd(prof + slot, now - t_prev);
-            t_prev = now;
-        }
-    };
+    TileStamp stamp(prof);
     for (;;) {
         __syncthreads();
         stamp(6);
@@ -658,16 +533,7 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_gen(const SvxPairDev*
         __syncthreads();
         const int tk = sh_ticket;
         if (tk >= total) break;
-        if (gpref[ecur + 1] <= tk) {
-            long long step = 1, lo = ecur + 1, hi = nent - 1;
-            while (lo + step < nent && gpref[lo + step] <= tk) { lo += step; step <<= 1; }
-            if (lo + step < hi) hi = lo + step;
-            while (lo < hi) {
-                const long long mid = (lo + hi + 1) >> 1;
-                if (gpref[mid] <= tk) lo = mid; else hi = mid - 1;
-            }
-            ecur = lo;
-        }
+        ecur = tile_entry(gpref, nent, tk, ecur);
         const int s = (int)(ecur / n_pairs);
         const SvxPairDev& P = pairs[ecur % n_pairs];
         const SvxLevel& Lv = P.lev[0];
@@ -681,129 +547,32 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_gen(const SvxPairDev*
 
         stamp(0);
         // ---- phase 1: cost planes, one group of types at a time, into this workgroup's scratch slice
-        char* stages[TG_S] = {BIGH ? lmain : st0, BIGH ? lmain + C::STAGE : st1, BIGH ? lmain + 2 * C::STAGE : st2,
-                              BIGH ? lmain + 3 * C::STAGE : st3};
+        // (individual stage pointers, never an array indexed by stage: svx_slab.h)
+        char* const rs0 = BIGH ? lmain : st0;
+        char* const rs1 = BIGH ? lmain + R::STAGE : st1;
+        char* const rs2 = BIGH ? lmain + 2 * R::STAGE : st2;
+        char* const rs3 = BIGH ? lmain + 3 * R::STAGE : st3;
+        const SlabSide sx{P.v[0], Lv.nrm[0], Lv.inv[0], X0, TL, xs}, sy{P.v[1], Lv.nrm[1], Lv.inv[1], Y0, TL, ys};
         for (int gi_ = 0; gi_ < plan.ng; gi_++) {
             const TileGroup& G = plan.g[gi_];
             __syncthreads();  // the previous group is finished with the ring and the row norms
-            constexpr int SPT = (TG_NSLOT * TL + TT_THREADS - 1) / TT_THREADS;
-#pragma unroll
-            for (int i = 0; i < SPT; i++) {
-                const int r = tid + i * TT_THREADS;
-                if (r < TG_NSLOT * TL) {
-                    float nv = 0.f, iv = 1.f;
-                    const int slot = r / TL, loc = r % TL;
-                    if (slot < G.nslot) {
-                        const int side = G.slot_info[slot] >> 7, layer = G.slot_info[slot] & 127;
-                        const int gi = (side ? Y0 : X0) + loc, nn = side ? ys : xs;
-                        if (gi >= 0 && gi < nn) {
-                            const size_t o = (size_t)layer * nn + gi;
-                            nv = Lv.nrm[side][o];
-                            if (Lv.inv[side]) iv = Lv.inv[side][o];
-                        }
-                    }
-                    snrm[r] = nv;
-                    sinv[r] = iv;
-                }
-            }
-            const char* src[PW];
-            unsigned live = 0;
-#pragma unroll
-            for (int i = 0; i < PW; i++) {
-                const int q = wave + TT_WAVES * i;
-                const int r = 16 * q + (lane >> 2);
-                const int slot = r / TL, loc = r % TL;
-                const int piece = (lane & 3) ^ swz_t(lane >> 2);
-                src[i] = reinterpret_cast<const char*>(tile_zero16);
-                if (slot < G.nslot) {
-                    const int side = G.slot_info[slot] >> 7, layer = G.slot_info[slot] & 127;
-                    const int gi = (side ? Y0 : X0) + loc, nn = side ? ys : xs;
-                    if (gi >= 0 && gi < nn) {
-                        src[i] = reinterpret_cast<const char*>(P.v[side]) + ((size_t)layer * nn + gi) * rowbytes + piece * 16;
-                        live |= 1u << i;
-                    }
-                }
-            }
-            const int piece_byte = ((lane & 3) ^ swz_t(lane >> 2)) * 16;
-            auto issue = [&](int k, char* stage) {
-#pragma unroll
-                for (int i = 0; i < PW; i++) {
-                    const char* s2 = src[i] + (size_t)k * TT_SLAB;
-                    if (!((live >> i) & 1u) || k * TT_SLAB + piece_byte >= rowbytes) s2 = reinterpret_cast<const char*>(tile_zero16);
-                    __builtin_amdgcn_global_load_lds((gptr_t)s2, (lptr_t)(stage + (wave + TT_WAVES * i) * 1024), 16, 0, 0);
-                }
-            };
+            auto slot_of = [&](int slot) { return slot < G.nslot ? SlabSlot{G.slot_info[slot] >> 7, G.slot_info[slot] & 127} : SlabSlot{-1, 0}; };
+            auto type_slots = [&](int tl) { return SlabPair{G.type_slots[tl] & 15, G.type_slots[tl] >> 4}; };
+            float r_nrm[R::SPT], r_inv[R::SPT];   // (stored at once: no registers to spare across this k loop)
+            R::row_scalars(slot_of, sx, sy, tid, r_nrm, r_inv);
+            R::store_scalars(snrm, sinv, tid, r_nrm, r_inv);
+            typename R::Src src;
+            R::sources(slot_of, sx, sy, rowbytes, wave, lane, src);
             f32x4_t acc[TG_UPW][2];
-            int aoff[TG_UPW], boffb[TG_UPW];
+            typename R::template Units<TG_UPW> un;
             const int nunits = G.nt * 2;
-#pragma unroll
-            for (int u2 = 0; u2 < TG_UPW; u2++) {
-                acc[u2][0] = acc[u2][1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-                const int u = wave + TT_WAVES * u2;
-                const int tl = u < nunits ? u / 2 : 0, xt = u % 2;
-                const int tsl = G.type_slots[tl];
-                aoff[u2] = ((tsl & 15) * TL + xt * 16) * TT_SLAB + loff;
-                boffb[u2] = ((tsl >> 4) * TL) * TT_SLAB + loff;
-            }
-            auto mma = [&](const char* stage) {
-                uint4 fa[TG_UPW], fb[TG_UPW][2];
-#pragma unroll
-                for (int u2 = 0; u2 < TG_UPW; u2++)
-                    if (wave + TT_WAVES * u2 < nunits) {
-                        fa[u2] = *reinterpret_cast<const uint4*>(stage + aoff[u2]);
-                        fb[u2][0] = *reinterpret_cast<const uint4*>(stage + boffb[u2]);
-                        fb[u2][1] = *reinterpret_cast<const uint4*>(stage + boffb[u2] + 16 * TT_SLAB);
-                    }
-#pragma unroll
-                for (int u2 = 0; u2 < TG_UPW; u2++)
-                    if (wave + TT_WAVES * u2 < nunits) {
-                        mma_t16<E>(acc[u2][0], fa[u2], fb[u2][0]);
-                        mma_t16<E>(acc[u2][1], fa[u2], fb[u2][1]);
-                    }
-            };
-            static_assert(3 * PW <= 63, "vmcnt range");
-#pragma unroll
-            for (int k = 0; k < TG_S - 1; k++)
-                if (k < NK) issue(k, stages[k]);
-            auto step = [&](int k, const char* rd, char* wr) {
-                if (k < NK) {
-                    const int younger = (NK - 1 - k) < (TG_S - 2) ? (NK - 1 - k) : (TG_S - 2);
-                    if (younger >= 2) wait_vm_t<2 * PW>();
-                    else if (younger == 1) wait_vm_t<PW>();
-                    else wait_vm_t<0>();
-                    __builtin_amdgcn_s_barrier();
-                    asm volatile("" ::: "memory");
-                    if (k + TG_S - 1 < NK) issue(k + TG_S - 1, wr);
-                    mma(rd);
-                }
-            };
-            for (int k0 = 0; k0 < NK; k0 += TG_S) {
-                step(k0, stages[0], stages[3]);
-                step(k0 + 1, stages[1], stages[0]);
-                step(k0 + 2, stages[2], stages[1]);
-                step(k0 + 3, stages[3], stages[2]);
-            }
-#pragma unroll
-            for (int u2 = 0; u2 < TG_UPW; u2++) {
-                const int u = wave + TT_WAVES * u2;
-                if (u >= nunits) continue;
-                const int tl = u / 2, xt = u % 2;
+            R::template units<TG_UPW, 2>(type_slots, nunits, nullptr, wave, lane, un, acc);
+            R::template run<TG_UPW, 2>(NK, src, un, acc, rs0, rs1, rs2, rs3, nullptr);
+            tile_cost_planes<TG_UPW, 8>(acc, nunits, wave, lane, snrm, sinv, [&](int tl) {
                 const int t = G.type_id[tl];
-                const int p = tpk[t] & 255, q = tpk[t] >> 8;
-                const int xsl = (G.type_slots[tl] & 15) * TL, ysl = (G.type_slots[tl] >> 4) * TL;
-                float* plt = pl + (size_t)(t >> 3) * (TL * TL * 8) + (t & 7);
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    const int yloc = 16 * j + lrow;
-                    const float ny = snrm[ysl + yloc], iy = sinv[ysl + yloc];
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int xloc = 16 * xt + 4 * lkg + r;
-                        const float sumx = acc[u2][j][r] * sinv[xsl + xloc] * iy;
-                        plt[(xloc * TL + yloc) * 8] = cost_formula_t(sumx, p, q, snrm[xsl + xloc], ny);
-                    }
-                }
-            }
+                return TilePlane{tpk[t] & 255, tpk[t] >> 8, (G.type_slots[tl] & 15) * TL, (G.type_slots[tl] >> 4) * TL,
+                                 pl + (size_t)(t >> 3) * (TL * TL * 8) + (t & 7)};
+            });
         }
         const int abase = TL * s - HX - HY;
         for (int i = tid; i < 2 * TL + HX + HY; i += TT_THREADS) {
