@@ -691,6 +691,34 @@ int svx_path_slack(svx_ctx *ctx, const float *costs, const int32_t *b_offset_in,
 int svx_row_slack(svx_ctx *ctx, double *const *slack /* HOST [n_pairs] of device [n+m+2] */,
                   int32_t *summary /* device [n_pairs][4], 16-byte aligned */, int n_pairs);
 
+/* svx_row_slack_wide: svx_row_slack for a last call that ran the tile sweep -- a band above 64 cells in the straight, dense
+ * and around-wide modes (csrc/svx_tiles_bwd.hip).  The definition above is unchanged: cells, kinds, E, E_b, F,
+ * Bk, the cut, the row's own edge and any duplicate of its move in the list excluded, NaN for a row that is no edge, not
+ * clamped.  The one new statement: w is the tile sweep's own cost, the fp32 value its LDS planes hold (the forward sweep
+ * keeps no cost array; the value is recomputed from the same rows by the same code).  Every candidate is still one
+ * (Bk) or two (the cut) singly rounded float64 additions in the order w + Bk(v), (F(u) + w) + Bk(v), and a minimum does not
+ * depend on its order: on equal cost bits the result is svx_path_slack's bits.
+ * How: a backward tile sweep over the forward call's tile plan, tickets reversed, computes Bk tile by tile and, for every
+ * edge u -> v it relaxes, folds ((F(u) + w) + Bk(v)) into the cuts a(u) <= c < a(v) unless the edge is the returned path's
+ * own; cutmin[c] is a per-diagonal minimum (64-bit atomic minimum per (tile, cut)), slack[r] = cutmin[x_start + y_start] -
+ * F(end).  One more tile sweep, no cost tensor.
+ * sw (HOST [n_pairs]): slack (device [n + m + 2] double; NULL skips the pair: nothing of it is written) and bsum (device
+ *   [A+2][B] double, A the level's path length, at least (n + m + 6) rows; NULL: the plane lives in the post-processing
+ *   scratch).  A given bsum receives Bk on the lattice nodes that are band cells; its other cells are unspecified.
+ * summary, failed pairs, the rules (LAST call on the context, svx_flush first, asynchronous): as svx_row_slack.
+ * SVX_ERR_ARG with text, nothing queued: the last call did not run the tile sweep (svx_row_slack measures it); its type set
+ * takes the general tile shape (k_band_tiles_gen; no backward sweep yet); no earlier successful call; a pair count that
+ * differs; a null sw / summary; summary not 16-byte aligned; slack or bsum not 8-byte aligned; a negative n_pairs.
+ * Launches: the node table, the persistent sweep (one workgroup per CU), the slack kernel.  The scratch -- descriptors, per
+ * pair cutmin and node table of (path capacity + 2) entries, tile flags, and the plane when it is not the caller's -- is the
+ * context's post-processing scratch (svx_scratch_bytes).  Stage name for svx_stage_ms: "tiles_bwd". */
+typedef struct svx_slack_wide {
+    double *slack;             /* device [n+m+2], NULL: skip the pair */
+    double *bsum;              /* device [A+2][B], nullable */
+} svx_slack_wide;
+int svx_row_slack_wide(svx_ctx *ctx, const svx_slack_wide *sw /* HOST [n_pairs] */,
+                       int32_t *summary /* device [n_pairs][4], 16-byte aligned */, int n_pairs);
+
 /* ---- row alternatives: what would the DP have done instead? (csrc/svx_alt.hip) ----------------------
  * Slack says how decided a row is.  These entries name the competitor: the edge that wins the row's cut when the row is
  * forbidden, and the rows of the best path through that edge that replace returned rows (its detour).  For rows the
@@ -821,6 +849,7 @@ int svx_copy_to_host(svx_ctx *ctx, void *dst_host, const void *src_device, int64
  * "band_costs0" "band_costsN" "band_dp0" "band_dpN" "path0" "traceback0" "traceback" "setup" "total" (0 = level 0, N = the
  * deeper levels; "path" and "traceback" without a digit are the deeper levels),
  * "tiles" (the wide-band tile sweep of SVX_SEARCH_STRAIGHT: costs + DP);
+ * "tiles_bwd" (svx_row_slack_wide: node table, backward tile sweep, slack kernel; set by that call);
  * "host_plan"/"host_launch" are host wall-clock.  -1 if unknown.
  * svx_set_profiling(ctx, 2): accumulate -- the events are recorded as with 1 but a call neither reads them nor waits
  * for its stream, so calls keep queueing behind one another; svx_stage_ms / svx_stage_launches then return the

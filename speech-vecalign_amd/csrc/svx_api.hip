@@ -28,11 +28,11 @@ int svx_fail(svx_ctx* ctx, int code, const char* fmt, ...) {
 static const char* kStageNames[] = {"pyr0",       "pyrN",     "pyr_aux",      "knob_scoresN", "knob",      "dense_costs",
                                     "dense_dp",   "path",     "band_costs0",  "band_costsN",  "band_dp0",  "band_dpN",
                                     "traceback",  "setup",    "total",        "host_plan",    "host_launch", "knob_sort", "knob_scores0", "pyr1", "tiles",
-                                    "traceback0", "path0"};
+                                    "traceback0", "path0", "tiles_bwd"};
 enum {
     S_PYR0 = 0, S_PYRN, S_PYR_AUX, S_KNOB_SCORES, S_KNOB, S_DENSE_COSTS, S_DENSE_DP, S_PATH, S_BAND_COSTS0, S_BAND_COSTSN,
     S_BAND_DP0, S_BAND_DPN, S_TRACEBACK, S_SETUP, S_TOTAL, S_HOST_PLAN, S_HOST_LAUNCH, S_KNOB_SORT, S_KNOB_SCORES0, S_PYR1, S_TILES,
-    S_TRACEBACK0, S_PATH0, S_COUNT
+    S_TRACEBACK0, S_PATH0, S_TILES_BWD, S_COUNT
 };
 
 struct StageRec {
@@ -127,6 +127,22 @@ struct StageScope {
 static void drop_pending(svx_ctx_ext* c) {
     for (auto& r : c->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     c->pending.clear();
+}
+
+// The event pairs the stages of a call recorded.  Mode 2: they join the pending ones, unread (the first query reads them).
+// Mode 1: read into ms[] now; the caller has waited for the streams they were recorded on.
+static void settle_recs(svx_ctx_ext* c) {
+    if (c->profiling == 2) {
+        for (auto& r : c->recs) c->pending.push_back(r);
+    } else {
+        for (auto& r : c->recs) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) c->ms[r.stage] += ms;
+            (void)hipEventDestroy(r.a);
+            (void)hipEventDestroy(r.b);
+        }
+    }
+    c->recs.clear();
 }
 
 extern "C" {
@@ -1319,21 +1335,14 @@ static int align_impl(svx_ctx* ctx, const svx_align_params* prm, const svx_pair*
     cx->ms[S_HOST_LAUNCH] = std::chrono::duration<double, std::milli>(t_done - t_enter).count() - plan_ms;
     if (ctx->profiling == 2) {
         // accumulate: nothing is read and nothing waits here, the next call can be launched behind this one
-        for (auto& r : cx->recs) cx->pending.push_back(r);
-        cx->recs.clear();
+        settle_recs(cx);
         for (int i = 0; i < S_COUNT; i++) cx->acc_launches[i] += cx->launches[i];
         cx->acc_ms[S_HOST_PLAN] += cx->ms[S_HOST_PLAN];
         cx->acc_ms[S_HOST_LAUNCH] += cx->ms[S_HOST_LAUNCH];
     } else if (ctx->profiling) {
         if ((rc = svx_synchronize(ctx))) return rc;
         if (cx->side_ready) { SVX_HIP(ctx, hipStreamSynchronize(cx->side)); SVX_HIP(ctx, hipStreamSynchronize(cx->helper)); }
-        for (auto& r : cx->recs) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) cx->ms[r.stage] += ms;
-            (void)hipEventDestroy(r.a);
-            (void)hipEventDestroy(r.b);
-        }
-        cx->recs.clear();
+        settle_recs(cx);
     }
     return SVX_OK;
 }
@@ -1350,4 +1359,86 @@ extern "C" int svx_align_around(svx_ctx* ctx, const svx_align_params* prm, const
     if (n_pairs <= 0) return SVX_OK;
     for (int p = 0; p < n_pairs; p++) NEED(ctx, pairs[p].align && pairs[p].info, "svx_align_around: pair %d: null pointer", p);
     return align_impl(ctx, prm, pairs, priors, n_pairs);
+}
+
+// ------------------------------------------------------------------------------ row slack in wide bands (svx_tiles_bwd.hip)
+// Scratch: [BwdPair descriptors] uploaded | per pair cutmin [cap + 2] u64 and the node table [cap + 2][2] int (filled with
+// ones) | per pair the tile flags [t_cap], then the ticket (zeros) | per pair without a caller's plane: Bk [cap + 2][B].
+// The tile plan -- t_lo, t_cnt, t_pref in the pairs' records, the ticket table -- is read where the forward call left it:
+// the half's arena is only rewritten by the next svx_align_batch / svx_align_around call, and last_ok says that none failed
+// half way since.
+extern "C" int svx_row_slack_wide(svx_ctx* ctx, const svx_slack_wide* sw, int32_t* summary, int n_pairs) {
+    if (!ctx) return svx_fail(nullptr, SVX_ERR_ARG, "svx_row_slack_wide: ctx is NULL");
+    NEED(ctx, sw && summary, "svx_row_slack_wide: null argument");
+    NEED(ctx, aligned16(summary), "svx_row_slack_wide: summary must be 16-byte aligned");
+    NEED(ctx, n_pairs >= 0, "svx_row_slack_wide: negative n_pairs");
+    for (int p = 0; p < n_pairs; p++)
+        NEED(ctx, (reinterpret_cast<uintptr_t>(sw[p].slack) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sw[p].bsum) & 7u) == 0,
+             "svx_row_slack_wide: pair %d: slack and bsum must be 8-byte aligned", p);
+    svx_ctx_ext* cx = X(ctx);
+    HalfState& H = cx->half[0];
+    if (cx->last_ok) {
+        NEED(ctx, H.bp.tiles, "svx_row_slack_wide: the last call did not run the tile sweep (a band of %d cells keeps its cost array): "
+             "svx_row_slack measures it", cx->last_band);
+        NEED(ctx, svxl_band_tiles_shape(H.bp.tfinal) < 2, "svx_row_slack_wide: %d alignment types take the general tile shape, which has "
+             "no backward sweep", H.bp.tfinal.n);
+    }
+    SvxLastCall lc;
+    int rc = svxl_last_call(ctx, "svx_row_slack_wide", n_pairs, nullptr, &lc);
+    if (rc) return rc;
+    NEED(ctx, cx->last_split == 0 && H.n_pairs == n_pairs, "svx_row_slack_wide: the tile sweep runs unpipelined");
+    const int B = lc.band;
+    const size_t b_desc = up256((size_t)n_pairs * sizeof(BwdPair));
+    size_t b_ones = 0, b_zero = 256, b_planes = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        if (!sw[p].slack) continue;
+        const SvxPairDev& P = lc.pair(p);
+        const size_t cap2 = (size_t)P.lev[0].path_cap + 2;
+        b_ones += 2 * up256(cap2 * 8);
+        b_zero += up256((size_t)P.t_cap * sizeof(int));
+        if (!sw[p].bsum) b_planes += up256(cap2 * B * sizeof(double));
+    }
+    char *pin, *dev;
+    rc = svxl_scratch_begin(ctx, "svx_row_slack_wide", b_desc, b_desc + b_ones + b_zero + b_planes, &pin, &dev);
+    if (rc) return rc;
+    BwdPair* hp = reinterpret_cast<BwdPair*>(pin);
+    char* at_ones = dev + b_desc;
+    char* at_zero = at_ones + b_ones;
+    char* at_plane = at_zero + b_zero;
+    int* ticket = reinterpret_cast<int*>(at_zero);
+    at_zero += 256;
+    for (int p = 0; p < n_pairs; p++) {
+        hp[p] = BwdPair{};
+        hp[p].summary = summary + 4 * (size_t)p;
+        if (!sw[p].slack) continue;
+        const SvxPairDev& P = lc.pair(p);
+        const size_t cap2 = (size_t)P.lev[0].path_cap + 2;
+        hp[p].slack = sw[p].slack;
+        hp[p].cutmin = reinterpret_cast<unsigned long long*>(at_ones);
+        hp[p].tab = reinterpret_cast<int*>(at_ones + up256(cap2 * 8));
+        at_ones += 2 * up256(cap2 * 8);
+        hp[p].flag = reinterpret_cast<int*>(at_zero);
+        at_zero += up256((size_t)P.t_cap * sizeof(int));
+        if (sw[p].bsum) hp[p].bsum = sw[p].bsum;
+        else { hp[p].bsum = reinterpret_cast<double*>(at_plane); at_plane += up256(cap2 * B * sizeof(double)); }
+    }
+    rc = svxl_scratch_upload(ctx, (size_t)n_pairs * sizeof(BwdPair));
+    if (rc) return rc;
+    if (b_ones) SVX_HIP(ctx, hipMemsetAsync(dev + b_desc, 0xFF, b_ones, ctx->stream));
+    SVX_HIP(ctx, hipMemsetAsync(dev + b_desc + b_ones, 0, b_zero, ctx->stream));
+    {
+        StageScope sc(ctx, S_TILES_BWD);
+        rc = svxl_band_tiles_bwd(ctx, H.dpairs, reinterpret_cast<const BwdPair*>(dev), n_pairs, H.bp.tfinal, H.bp.W, H.bp.dtype, H.max_tnd,
+                                 reinterpret_cast<const int*>(H.arena + H.o_tickets), ticket);
+    }
+    // stage time, also of a call that failed half way (its event pair is not left for the next align call to find): mode 2
+    // leaves it with the pending ones; mode 1 reads it now, behind the stream
+    if (ctx->profiling == 2) {
+        cx->acc_launches[S_TILES_BWD]++;
+    } else if (ctx->profiling) {
+        (void)hipStreamSynchronize(ctx->stream);
+        cx->ms[S_TILES_BWD] = 0.0;
+    }
+    if (ctx->profiling) settle_recs(cx);
+    return rc;
 }

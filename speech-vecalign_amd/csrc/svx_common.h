@@ -256,7 +256,8 @@ struct svx_ctx {
     // offsets, compacted rows), svx_knn_search_groups (svx_groupsearch.hip: offsets, workgroup table) and svx_time_prior
     // (svx_prior.hip: descriptors, prefix counts), svx_band_contact and svx_align_widen (svx_contact.hip: descriptors, the
     // report rows, the staged priors of a round), svx_score_alignments (svx_given.hip: descriptors, chunk table, partial sums)
-    // svx_row_slack (svx_slack.hip: one array of PlanePair descriptors, svx_plane.h, then one backward plane per pair) and
+    // svx_row_slack (svx_slack.hip: one array of PlanePair descriptors, svx_plane.h, then one backward plane per pair),
+    // svx_row_slack_wide (svx_api.hip: BwdPair descriptors, cut minima and node tables, tile flags and the ticket, Bk planes) and
     // svx_row_alternatives / svx_path_alternatives (svx_alt.hip: the same one array, then per pair one backward plane and one
     // node table).  They go through svxl_scratch_begin / svxl_scratch_upload only.
     char* post_buf;
@@ -322,6 +323,18 @@ int svxl_band_tiles_shape(const SvxTypes& types);
 size_t svxl_band_tiles_scratch(const SvxTypes& types);
 int svxl_band_tiles_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, const SvxTypes& types, int W, int dtype, int max_nd,
                           int* gpref, int* ticket, float* planes);
+// the backward tile sweep with the fused cut minimum (svx_tiles_bwd.hip): what svx_row_slack_wide adds to a pair's record.
+// The tile plan and the ticket table are the forward call's.
+struct BwdPair {
+    double* slack;                 // [n + m + 2]; null: the pair is skipped
+    double* bsum;                  // [A+2][B] the Bk plane (the caller's, or in the post-processing scratch)
+    unsigned long long* cutmin;    // [A+2] monotone integer images of the cut minima, all ones = none
+    int* tab;                      // [A+2][2] the returned path's node on each diagonal: y, x_len | y_len << 8; -1 none
+    int* flag;                     // [t_cap] tile finished (this sweep's own flags)
+    int32_t* summary;              // [4]
+};
+int svxl_band_tiles_bwd(svx_ctx*, const SvxPairDev* pairs, const BwdPair* bw, int n_pairs, const SvxTypes& types, int W, int dtype,
+                        int max_nd, const int* gpref, int* ticket);
 // dp (svx_dp.hip)
 int svxl_dense_dp(svx_ctx*, const float* cost, int s0, int s1, float pen, double* csum, int* bp);
 int svxl_dense_stage_batch(svx_ctx*, const SvxPairDev* pairs, int n_pairs, int max_s0);

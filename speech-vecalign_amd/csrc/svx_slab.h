@@ -1,6 +1,7 @@
 // svx_slab.h -- the LDS-DMA slab ring of the band-cost kernel (svx_band.hip: band2_block) and of the tile sweep's cost
-// phase (svx_tiles.hip: k_band_tiles, k_band_tiles_gen), and the small device helpers the cost kernels share (those also
-// serve svx_costs.hip, svx_given.hip and band3_block).  DESIGN.md 5 and 6.  Device code only, gfx950 only.
+// phase (svx_tiles.hip: k_band_tiles, k_band_tiles_gen; svx_tiles_bwd.hip: k_band_tiles_bwd), and the small device helpers
+// the cost kernels share (those also serve svx_costs.hip, svx_given.hip and band3_block).  DESIGN.md 5, 6 and 6f.  Device
+// code only, gfx950 only.
 //
 // The ring: rows travel global -> LDS by LDS-DMA (global_load_lds_dwordx4, no VGPR stop-over, no ds_write) in 64-byte
 // k-slabs = one MFMA k-step, into S stages: slab k is multiplied out of stage k % S while slabs k + 1 .. k + S - 2 are
@@ -77,8 +78,9 @@ struct SlabSide {
     const float* inv;
     int org, rows, lim;
 };
-struct SlabSlot {   // what a stage slot holds; side < 0: nothing
-    int side, layer;
+struct SlabSlot {   // what a stage slot holds; side < 0: nothing.  shift: the slot stages rows org + shift ... of its side
+    int side, layer;   // (the backward tile sweep prices the edges LEAVING its nodes: layer k, k rows further on)
+    int shift = 0;
 };
 struct SlabPair {   // the slots an alignment type multiplies
     int x, y;
@@ -122,7 +124,7 @@ struct SlabRing {
             const SlabSlot sl = slot_of(slot);
             if (sl.side >= 0) {
                 const int side = sl.side;
-                const int gi = (side ? sy.org : sx.org) + loc, nn = side ? sy.lim : sx.lim;
+                const int gi = (side ? sy.org : sx.org) + loc + sl.shift, nn = side ? sy.lim : sx.lim;
                 if (loc < (side ? sy.rows : sx.rows) && gi >= 0 && gi < nn) {
                     const size_t o = (size_t)sl.layer * nn + gi;
                     nrm[i] = (side ? sy.nrm : sx.nrm)[o];
@@ -160,7 +162,7 @@ struct SlabRing {
             const SlabSlot sl = slot_of(slot);
             if (sl.side >= 0) {
                 const int side = sl.side;
-                const int gi = (side ? sy.org : sx.org) + loc, nn = side ? sy.lim : sx.lim;
+                const int gi = (side ? sy.org : sx.org) + loc + sl.shift, nn = side ? sy.lim : sx.lim;
                 if (loc < (side ? sy.rows : sx.rows) && gi >= 0 && gi < nn) {
                     s.p[i] = reinterpret_cast<const char*>(side ? sy.v : sx.v) + ((size_t)sl.layer * nn + gi) * rowbytes + piece * 16;
                     s.live |= 1u << i;

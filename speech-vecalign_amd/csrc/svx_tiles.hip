@@ -21,25 +21,17 @@
 // Results go to the reference's node arrays (csum [A+2][B] float64, packed back-pointers), which the existing
 // traceback kernel walks.  Type sets beyond these two LDS-resident shapes run k_band_tiles_gen below (planes through
 // a per-workgroup slice of global scratch, halo of the largest step, int32 back-pointers for steps above 15).
+// What the backward sweep of svx_tiles_bwd.hip shares with this file (tile geometry, TilePlan, the cost-plane epilogue) is
+// in svx_tile_plan.h.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "svx_common.h"
 #include "svx_slab.h"
+#include "svx_tile_plan.h"
 
 namespace {
-
-constexpr int TL = 32;             // tile side in DP nodes
-constexpr int TT_THREADS = 256, TT_WAVES = 4, TT_SLAB = SLAB_BYTES;
-constexpr int TT_MAXSLOT = 12, TT_MAXT = 16, TT_HALO = 8;
-constexpr int CS_W = TL + TT_HALO;  // csum tile with halo
-
-struct TilePlan {
-    int nt, nslot, halo;
-    int slot_info[TT_MAXSLOT];  // side << 8 | layer
-    int type_slots[TT_MAXT];    // x slot | y slot << 8
-};
 
 // b_offset_out of a pair, then per tile anti-diagonal s the run of tiles (I, s - I) that hold band nodes.  Everything
 // comes from the level's search path: the straight line, or the path of a prior (SVX_SEARCH_AROUND_WIDE).  The run is
@@ -129,27 +121,6 @@ __global__ __launch_bounds__(1024) void k_tile_prefix(const SvxPairDev* __restri
     }
 }
 
-template <typename E, int NSLOT, int UPW, int S>
-struct TileCfg {
-    using Ring = SlabRing<E, TL, NSLOT, TT_WAVES, S>;   // svx_slab.h: stage size, DMA pieces, the k loop
-    static constexpr int TPP = TT_WAVES * UPW / 2;
-    static_assert(TPP <= TT_MAXT && NSLOT <= TT_MAXSLOT, "plan limits");
-};
-
-// (diagnostic build-in: with SVX_TILE_PROF=1 thread 0 sums the 100 MHz ticks of every phase into prof[0..6])
-struct TileStamp {
-    unsigned long long* prof;
-    unsigned long long t_prev;
-    __device__ __forceinline__ explicit TileStamp(unsigned long long* p) : prof(p), t_prev(p ? __builtin_amdgcn_s_memrealtime() : 0) {}
-    __device__ __forceinline__ void operator()(int slot) {
-        if (prof && threadIdx.x == 0) {
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            atomicAdd(prof + slot, now - t_prev);
-            t_prev = now;
-        }
-    }
-};
-
 // The (diagonal, pair) entry of ticket tk: the last e with gpref[e] <= tk, searched forward from the workgroup's previous
 // entry (tickets grow).  Gallop, then bisect: a workgroup's next ticket is usually a few entries ahead.
 __device__ __forceinline__ long long tile_entry(const int* __restrict__ gpref, long long nent, int tk, long long ecur) {
@@ -164,38 +135,6 @@ __device__ __forceinline__ long long tile_entry(const int* __restrict__ gpref, l
         ecur = lo;
     }
     return ecur;
-}
-
-// The cost planes of a wave's units: accumulators x the two inverse norms -> costs in double like the reference.
-// plane_of(type of the pass) names the type's sizes, the first staged rows of its two slots and where the plane goes:
-// cell (x row, y row) at dst[(x * TL + y) * YS] -- YS = 1: the LDS planes of k_band_tiles, 8: k_band_tiles_gen's
-// slice of global scratch.
-struct TilePlane {
-    int p, q, xsl, ysl;
-    float* dst;
-};
-template <int UPW, int YS, class PlaneOf>
-__device__ __forceinline__ void tile_cost_planes(const f32x4_t (&acc)[UPW][2], int nunits, int wave, int lane, const float* snrm,
-                                                 const float* sinv, PlaneOf plane_of) {
-    const int lrow = lane & 15, lkg = lane >> 4;
-#pragma unroll
-    for (int u2 = 0; u2 < UPW; u2++) {
-        const int u = wave + TT_WAVES * u2;
-        if (u >= nunits) continue;
-        const int xt = u % 2;
-        const TilePlane tp = plane_of(u / 2);
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int yloc = 16 * j + lrow;
-            const float ny = snrm[tp.ysl + yloc], iy = sinv[tp.ysl + yloc];
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int xloc = 16 * xt + 4 * lkg + r;
-                const float sumx = acc[u2][j][r] * sinv[tp.xsl + xloc] * iy;
-                tp.dst[(xloc * TL + yloc) * YS] = cost_formula(sumx, tp.p, tp.q, snrm[tp.xsl + xloc], ny);
-            }
-        }
-    }
 }
 
 struct DpMerge {
@@ -819,28 +758,6 @@ bool make_tile_plan_gen(const SvxTypes& ty, TilePlanGen* plan, double* restream)
     return true;
 }
 
-bool make_tile_plan(const SvxTypes& ty, int tpp, int nslot_max, TilePlan* plan) {
-    memset(plan, 0, sizeof(*plan));
-    if (ty.n < 1 || ty.n > tpp) return false;
-    int xs[SVX_MAX_TYPES + 2], ys[SVX_MAX_TYPES + 2];
-    memset(xs, 0, sizeof(xs));
-    memset(ys, 0, sizeof(ys));
-    int halo = 1;
-    for (int t = 0; t < ty.n; t++) {
-        const int lx = ty.x[t] - 1, ly = ty.y[t] - 1;
-        if (ty.x[t] > 15 || ty.y[t] > 15) return false;  // packed back-pointers
-        if (!xs[lx]) { if (plan->nslot >= nslot_max) return false; plan->slot_info[plan->nslot] = lx; xs[lx] = ++plan->nslot; }
-        if (!ys[ly]) { if (plan->nslot >= nslot_max) return false; plan->slot_info[plan->nslot] = (1 << 8) | ly; ys[ly] = ++plan->nslot; }
-        plan->type_slots[t] = (xs[lx] - 1) | ((ys[ly] - 1) << 8);
-        if (ty.x[t] > halo) halo = ty.x[t];
-        if (ty.y[t] > halo) halo = ty.y[t];
-    }
-    if (halo > TT_HALO) return false;
-    plan->nt = ty.n;
-    plan->halo = halo;
-    return true;
-}
-
 }  // namespace
 
 // Which tile shape takes this type set: 0 = <= 10 types on <= 8 layers, 1 = <= 16 types on <= 12 layers (both with
@@ -851,13 +768,6 @@ int svxl_band_tiles_shape(const SvxTypes& types) {
     if (make_tile_plan(types, 16, 12, &plan)) return 1;
     TilePlanGen gp;
     return make_tile_plan_gen(types, &gp, nullptr) ? 2 : -1;
-}
-
-static int tile_cu_count() {
-    int dev = 0, ncu = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    return ncu;
 }
 
 // Global scratch of the general shape: one slice of cost planes per persistent workgroup (T rounded up to 8 planes of

@@ -88,6 +88,11 @@ class Given(ctypes.Structure):
                 ("scores", c_vp), ("total", c_vp), ("report", c_vp)]
 
 
+class SlackWide(ctypes.Structure):
+    """svx_slack_wide: where the slack of one pair goes and, optionally, its Bk plane (svx_row_slack_wide)."""
+    _fields_ = [("slack", c_vp), ("bsum", c_vp)]
+
+
 class Alt(ctypes.Structure):
     """svx_alt: where the alternatives of one pair go (svx_row_alternatives, svx_path_alternatives)."""
     _fields_ = [("slack", c_vp), ("edge", c_vp), ("span", c_vp), ("detour", c_vp), ("detour_scores", c_vp),
@@ -167,6 +172,7 @@ _SIGS = {
                                 ctypes.POINTER(WidenParams), c_vp]),
     "svx_score_alignments": (c_int, [c_vp, ctypes.POINTER(Given), c_int]),
     "svx_row_slack": (c_int, [c_vp, ctypes.POINTER(c_vp), c_vp, c_int]),
+    "svx_row_slack_wide": (c_int, [c_vp, ctypes.POINTER(SlackWide), c_vp, c_int]),
     "svx_row_alternatives": (c_int, [c_vp, ctypes.POINTER(Alt), c_int, c_f64, c_vp, c_int]),
     "svx_path_alternatives": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_f64, c_int, c_int,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(Alt), c_int, c_f64]),

@@ -42,6 +42,11 @@ own alignment lines with a fourth field, the row's slack (svx_row_slack) -- the 
 does not contain the row, minus the total of the returned path: `[0, 1]:[0]:0.349737:0.012345`.  0 means a second optimum
 exists and the tie rule picked the row; a small value means the row is ambiguous (a repeated phrase, near-silent segments);
 several deletion penalties mean it is solid; `inf` means no other path exists in the band.  The alignment files do not change.
+--slack_wide_dir DIR writes the same files for a band above 64 cells (--mode band / dense / --prior_band), where the tile
+sweep keeps no cost array: the slack comes from a backward tile sweep (svx_row_slack_wide), same definition.  In --mode dense
+the band follows the documents: a batch whose documents all have at most 31 rows runs the band kernels and is measured by
+svx_row_slack, so one flag serves a corpus of mixed sizes.  Not with --widen (a follow-up: after band doubling the last device
+call holds only the pairs that were searched again, and slack would have to be measured round by round).
 
 --alt_dir DIR names the competitor behind a small slack (svx_row_alternatives): DIR/{src}-{tgt}/{s}-{t}.txt holds one
 tab-separated line per returned row that has a written detour -- row number, slack, lo, hi, then the detour's rows in the
@@ -137,6 +142,12 @@ def parse_args(argv=None):
                         "(svx_row_slack): best total of a path of the same band without the row minus the returned path's total, "
                         "%%.6f; 0 = tied with another optimum, inf = no other path.  Needs the band's cost array: not for bands above "
                         "64 cells in --mode band / dense / --prior_band (the tile sweep keeps none)")
+    p.add_argument("--slack_wide_dir", type=str, default=None,
+                   help="--slack_dir for bands above 64 cells (--mode band / dense / --prior_band): the same files, the slack "
+                        "measured by the backward tile sweep (svx_row_slack_wide), which needs no cost array.  Needs an alignment "
+                        "type set on an LDS-resident tile shape (at most 16 types on 12 overlap layers, sizes up to 8: -a 2 .. 6); "
+                        "narrower bands take --slack_dir (--mode dense: a batch of documents of at most 31 rows is measured that way "
+                        "by itself)")
     p.add_argument("--alt_dir", type=str, default=None,
                    help="also write {alt_dir}/{src}-{tgt}/{s}-{t}.txt: per returned row with a written detour one tab-separated line "
                         "'row slack lo hi detour rows...' (svx_row_alternatives): the rows of the best path of the same band without "
@@ -198,6 +209,9 @@ def parse_args(argv=None):
                 "that were searched again")
     if args.rescore_dir is not None and args.skip_existing:
         p.error("--rescore_dir cannot be combined with --skip_existing: a skipped pair has no costs to price a path with")
+    if args.slack_wide_dir is not None and args.slack_dir is not None:
+        p.error("--slack_wide_dir and --slack_dir measure the same rows: a band above 64 cells takes --slack_wide_dir, a "
+                "narrower one --slack_dir")
     if args.slack_dir is not None:
         if args.widen:
             p.error("--slack_dir cannot be combined with --widen: after band doubling the last device call holds only the pairs "
@@ -208,6 +222,21 @@ def parse_args(argv=None):
         if cells is not None and cells > 64:   # (--mode dense: the band follows the documents; the library refuses it)
             p.error(f"--slack_dir needs the band's cost array: a band of {cells} cells runs the tile sweep, which keeps no cost "
                     "array (at most 64 cells in --mode band and with --prior_band)")
+    if args.slack_wide_dir is not None:
+        if args.widen:
+            p.error("--slack_wide_dir cannot be combined with --widen: after band doubling the last device call holds only the pairs "
+                    "that were searched again")
+        if args.skip_existing:
+            p.error("--slack_wide_dir cannot be combined with --skip_existing: a skipped pair has no costs to measure slack with")
+        cells = 2 * max(3, (args.band + 1) // 2) if args.mode == "band" else (args.prior_band if args.mode == "around" else None)
+        if args.mode == "ref" or (args.mode != "dense" and (cells is None or cells <= 64)):
+            p.error("--slack_wide_dir measures the tile sweep, which runs bands above 64 cells in --mode band / dense and with "
+                    "--prior_band: this band keeps its cost array, use --slack_dir")
+        from ..vecalign.dp_utils import tile_shape
+        if tile_shape(resolve_search_params(args.alignment_max_size, None, args.search_buffer_size)[0]) not in (0, 1):
+            p.error(f"--slack_wide_dir: the alignment types of -a {args.alignment_max_size} take the general tile shape, which has "
+                    "no backward sweep (at most 16 types on 12 overlap layers: -a 2 .. 6); --slack_dir measures bands of at most "
+                    "64 cells with any type set")
     if args.regret_dir is not None and args.rescore_dir is None:
         p.error("--regret_dir needs --rescore_dir: the rows whose regret is wanted come from its files")
     if not 1 <= args.alt_max_detour <= 256:
@@ -536,9 +565,9 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
     if getattr(args, "post_dir", None) is not None:
         post_dir = Path(args.post_dir) / f"{args.src_lang}-{args.tgt_lang}"
         post_dir.mkdir(parents=True, exist_ok=True)
-    slack_dir = None
-    if getattr(args, "slack_dir", None) is not None:
-        slack_dir = Path(args.slack_dir) / f"{args.src_lang}-{args.tgt_lang}"
+    slack_dir, slack_wide = None, getattr(args, "slack_wide_dir", None) is not None
+    if getattr(args, "slack_dir", None) is not None or slack_wide:   # (one file format, two ways to measure)
+        slack_dir = Path(args.slack_wide_dir if slack_wide else args.slack_dir) / f"{args.src_lang}-{args.tgt_lang}"
         slack_dir.mkdir(parents=True, exist_ok=True)
     alt_dir, regret_dir = (None if getattr(args, flag, None) is None else Path(getattr(args, flag)) / f"{args.src_lang}-{args.tgt_lang}"
                            for flag in ("alt_dir", "regret_dir"))
@@ -687,7 +716,9 @@ def align_pairs(pairs: List[VecalignData], args, batch_size: int, io_threads: Op
                     pb.h_contact = torch.empty(contact.shape, dtype=contact.dtype, pin_memory=True)
                     pb.h_contact.copy_(contact, non_blocking=True)   # (lands before the event of fetch_async)
             if slack_dir is not None:   # one call behind run(); read back with the results
-                sl, _ = pb.row_slack()
+                # (--slack_wide_dir in --mode dense: the band follows the batch's documents, and a batch of documents of at most
+                #  31 rows runs the band kernels, which keep their cost array: svx_row_slack measures that one)
+                sl, _ = pb.row_slack_wide() if slack_wide and pb.took_tile_sweep() else pb.row_slack()
                 pb.h_slack = torch.empty(sl.shape, dtype=sl.dtype, pin_memory=True)
                 pb.h_slack.copy_(sl, non_blocking=True)
             if alt_dir is not None or regret_dir is not None:   # one call behind run(); read back with the results

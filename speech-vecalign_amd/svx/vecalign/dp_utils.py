@@ -272,6 +272,20 @@ def draw_indices_into(norm_out, knob_out, n, m, k0, k1, max_size_full_dp, costs_
 
 
 # ------------------------------------------------------------------------------------- batch
+def tile_shape(types):
+    """Host twin of the tile sweep's shape choice (csrc/svx_tiles.hip: svxl_band_tiles_shape): 0 = at most 10 types on at
+    most 8 overlap layers, 1 = at most 16 types on at most 12 layers (both with sizes up to 8: the LDS-resident shapes, which
+    have a backward sweep, svx_row_slack_wide), 2 = the general shape."""
+    types = [(int(x), int(y)) for x, y in types]
+    layers = len({x for x, _ in types}) + len({y for _, y in types})
+    if types and max(max(x, y) for x, y in types) <= 8:
+        if len(types) <= 10 and layers <= 8:
+            return 0
+        if len(types) <= 16 and layers <= 12:
+            return 1
+    return 2
+
+
 class PreparedBatch:
     """A batch of document pairs resident on the device, ready for `run()` (svx_align_batch).
     Everything the timed path touches -- embeddings, sampled indices, output buffers, descriptors --
@@ -586,6 +600,37 @@ class PreparedBatch:
         self.slack, self.slack_summary, self._slack_ptrs = slack, summary, ptrs   # alive as long as the batch
         ctx.hold(self)
         return slack, summary
+
+    def took_tile_sweep(self):
+        """Does run() take the wide-band tile sweep (a band above 64 cells in the straight and around modes), which keeps no
+        cost array?  Then row_slack_wide() measures slack, otherwise row_slack()."""
+        return int(self.prm.search_mode) != _lib.SVX_SEARCH_COARSE_TO_FINE and 2 * int(self.prm.width_over2) > 64
+
+    def row_slack_wide(self, return_plane=False):
+        """svx_row_slack_wide for the last run() on the context (include/svx.h): row_slack() for a run that took the tile
+        sweep -- the same definition, computed by a backward tile sweep that folds the cut minimum while it runs, with the
+        sweep's own fp32 costs.  -> (slack, summary) laid out as row_slack()'s.  return_plane: -> (slack, summary, planes),
+        planes[i] a float64 device tensor [n + m + 6, 2 * width_over2] holding Bk on the lattice nodes that are band cells of
+        diagonals 0 .. path length + 1 (other cells unspecified).  A last call on a band of at most 64 cells, or a type set
+        on the general tile shape, raises SvxError; so does a call behind run_widen(), whose last round holds only the pairs
+        it searched again.  Asynchronous on the current stream."""
+        ctx = self.ctx
+        t = ctx.torch
+        npairs = len(self.vecs)
+        ctx.use_current_stream()
+        slack = t.full((max(1, int(self.offs[-1])),), float("nan"), dtype=t.float64, device=ctx.tdev)
+        summary = t.zeros((npairs, 4), dtype=t.int32, device=ctx.tdev)
+        B = 2 * int(self.prm.width_over2)
+        planes = [t.full((int(a.shape[1]) + int(b.shape[1]) + 6, B), float("nan"), dtype=t.float64, device=ctx.tdev)
+                  for a, b in self.vecs] if return_plane else None
+        sw = (_lib.SlackWide * max(1, npairs))()
+        for i in range(npairs):
+            sw[i].slack = slack.data_ptr() + 8 * int(self.offs[i])
+            sw[i].bsum = planes[i].data_ptr() if return_plane else None
+        ctx.check(ctx.lib.svx_row_slack_wide(ctx.h, sw, _p(summary), npairs))
+        self.slack, self.slack_summary, self._slack_ptrs = slack, summary, (sw, planes)   # alive as long as the batch
+        ctx.hold(self)
+        return (slack, summary, planes) if return_plane else (slack, summary)
 
     def row_alternatives(self, max_detour=16, max_slack=float("inf"), given=None, detour=True, skip=()):
         """svx_row_alternatives for the last run() on the context (include/svx.h): per returned row at level 0 the edge that
@@ -910,8 +955,8 @@ def vecalign(vecs0, vecs1, final_alignment_types, del_percentile_frac, width_ove
         stack[0]['given'] = dict(verdict=search_error(own['total'], got['total'], got['report']), found_total=own['total'],
                                  given_total=got['total'], del_penalty=got['del_penalty'], report=got['report'],
                                  scores=got['scores'])
-    if return_slack:
-        sl, summ = pb.row_slack()
+    if return_slack:   # (a run on the tile sweep keeps no cost array: the backward tile sweep measures it)
+        sl, summ = pb.row_slack_wide() if pb.took_tile_sweep() else pb.row_slack()
         stack[0]['row_slack'] = sl.cpu().numpy()[:len(alignments)].copy()
         stack[0]['slack_summary'] = tuple(int(v) for v in summ.cpu().numpy()[0])
     if return_alternatives:

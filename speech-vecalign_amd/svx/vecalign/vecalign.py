@@ -137,7 +137,8 @@ def align(src: str, tgt: str, src_embed: List[str], src_stopes: bool, tgt_stopes
     (svx_row_alternatives; PreparedBatch.row_alternatives) --, refused where return_slack is.
     return_slack: also stack[0]['row_slack'], the slack of every final alignment -- the total of the best path of the same
     band without that row minus the total of the returned path (svx_row_slack) -- and stack[0]['slack_summary']; a band above
-    64 cells in the band / dense modes runs the tile sweep, which keeps no costs, and is refused."""
+    64 cells in the band / dense modes runs the tile sweep, which keeps no costs: its slack comes from the backward tile
+    sweep (svx_row_slack_wide), same definition.  (return_alternatives is still refused there.)"""
     if verbose:
         logger.setLevel(logging.DEBUG)
     types, src_k, tgt_k, width_over2 = resolve_search_params(alignment_max_size, many_to_one, search_buffer_size)
