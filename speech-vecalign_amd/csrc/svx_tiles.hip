@@ -21,8 +21,10 @@
 // Results go to the reference's node arrays (csum [A+2][B] float64, packed back-pointers), which the existing
 // traceback kernel walks.  Type sets beyond these two LDS-resident shapes run k_band_tiles_gen below (planes through
 // a per-workgroup slice of global scratch, halo of the largest step, int32 back-pointers for steps above 15).
-// What the backward sweep of svx_tiles_bwd.hip shares with this file (tile geometry, TilePlan, the cost-plane epilogue) is
-// in svx_tile_plan.h.
+// What the two kernels here and the backward sweep of svx_tiles_bwd.hip share is in svx_tile_plan.h: tile geometry, TilePlan,
+// the cost-plane epilogue, and the scaffold of the persistent loop (ticket claim, band offsets, neighbour wait, halo fill,
+// publish: every flag and every load of a neighbour's node, with the one argument why that hand-off is sound).  The kernels
+// below hold their cost phase and their node-diagonal loop.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -121,27 +123,6 @@ __global__ __launch_bounds__(1024) void k_tile_prefix(const SvxPairDev* __restri
     }
 }
 
-// The (diagonal, pair) entry of ticket tk: the last e with gpref[e] <= tk, searched forward from the workgroup's previous
-// entry (tickets grow).  Gallop, then bisect: a workgroup's next ticket is usually a few entries ahead.
-__device__ __forceinline__ long long tile_entry(const int* __restrict__ gpref, long long nent, int tk, long long ecur) {
-    if (gpref[ecur + 1] <= tk) {
-        long long step = 1, lo = ecur + 1, hi = nent - 1;
-        while (lo + step < nent && gpref[lo + step] <= tk) { lo += step; step <<= 1; }
-        if (lo + step < hi) hi = lo + step;
-        while (lo < hi) {
-            const long long mid = (lo + hi + 1) >> 1;
-            if (gpref[mid] <= tk) lo = mid; else hi = mid - 1;
-        }
-        ecur = lo;
-    }
-    return ecur;
-}
-
-struct DpMerge {
-    double tot;
-    int key;
-};
-
 template <typename E, int NSLOT, int UPW, int S>
 __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __restrict__ pairs, int n_pairs, SvxTypes ty, TilePlan plan,
                                                            int W, int max_nd, const int* __restrict__ gpref, int* ticket,
@@ -168,21 +149,15 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
     const int total = gpref[nent];
     for (int t = tid; t < NTt; t += TT_THREADS) tpk[t] = (int)ty.x[t] | ((int)ty.y[t] << 8);
     const double inf = __builtin_inf();
-    long long ecur = 0;  // tickets grow: the (diagonal, pair) entry of a workgroup's ticket only moves forward
+    long long ecur = 0;
 
     TileStamp stamp(prof);
     for (;;) {
-        __syncthreads();  // the previous tile is finished with LDS
-        stamp(6);
-        if (tid == 0) sh_ticket = atomicAdd(ticket, 1);
-        __syncthreads();
-        const int tk = sh_ticket;
-        if (tk >= total) break;
-        ecur = tile_entry(gpref, nent, tk, ecur);
-        const int s = (int)(ecur / n_pairs);
-        const SvxPairDev& P = pairs[ecur % n_pairs];
+        const TileAt at = tile_claim<false>(pairs, n_pairs, gpref, nent, total, ticket, &sh_ticket, ecur, stamp);
+        if (at.p < 0) break;
+        const int s = at.s, I = at.I, J = at.J;
+        const SvxPairDev& P = pairs[at.p];
         const SvxLevel& Lv = P.lev[0];
-        const int I = P.t_lo[s] + (tk - gpref[ecur]), J = s - I;
         const int xs = Lv.n[0], ys = Lv.n[1], d = P.d;
         const int rowbytes = d * (int)sizeof(St);
         const int NK = (rowbytes + TT_SLAB - 1) / TT_SLAB;
@@ -211,73 +186,20 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
         R::store_scalars(snrm, sinv, tid, r_nrm, r_inv);
         // band offsets of the node diagonals this tile and its halo touch: a in [32 s - 2 H, 32 s + 62]
         const int abase = TL * s - 2 * H;
-        for (int i = tid; i < 2 * TL + 2 * H; i += TT_THREADS) {
-            const int a = abase + i;
-            bo_l[i] = (a >= 0 && a < A + 2) ? Lv.boff_out[a] : (1 << 28);  // (no such diagonal: nothing is in its band)
-        }
+        tile_band_offsets(bo_l, Lv.boff_out, abase, 2 * TL + 2 * H, A);
         __syncthreads();
         tile_cost_planes<UPW, 1>(acc, nunits, wave, lane, snrm, sinv, [&](int tl) {
             return TilePlane{tpk[tl] & 255, tpk[tl] >> 8, (plan.type_slots[tl] & 255) * TL, (plan.type_slots[tl] >> 8) * TL, planes + tl * TL * TL};
         });
         stamp(1);
-        // ---- phase 2: wait for the neighbours (all three, when they exist, have smaller tickets), then their halo
-        if (tid == 0) {
-            const int nb[3][2] = {{I - 1, J}, {I, J - 1}, {I - 1, J - 1}};
-            for (int e = 0; e < 3; e++) {
-                const int ni = nb[e][0], nj = nb[e][1], ns = ni + nj;
-                if (ni < 0 || nj < 0) continue;
-                const int off = ni - P.t_lo[ns];
-                if (off < 0 || off >= P.t_cnt[ns]) continue;  // not a band tile: nothing to wait for
-                const int* flag = P.t_flag + P.t_pref[ns] + off;
-                // (bounded: a neighbour's ticket is smaller, so its workgroup is running; the bound only turns a
-                //  programming error into an error code instead of a hung GPU)
-                long spins = 0;
-                while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 && spins < (1l << 25)) {
-                    __builtin_amdgcn_s_sleep(2);
-                    spins++;
-                }
-                if (spins >= (1l << 25)) *P.status = SVX_ERR_HIP;
-            }
-        }
-        __syncthreads();
+        // ---- phase 2: wait for the neighbours (all three, when they exist, have smaller tickets), then their halo into the
+        // csum tile: position (i + 8, j + 8) <-> node (32 I + i, 32 J + j), i, j in [-H, 32); <= 3 halo positions per thread
+        // (the hand-off: svx_tile_plan.h)
+        const TileBand band{xs, ys, B, abase, bo_l};
+        const TileGeo geo{H, H, CS_W, TT_HALO, TT_HALO};
+        tile_wait<false>(P, P.t_flag, I, J, 1, 1);
         stamp(2);
-        // csum tile: position (i + 8, j + 8) <-> node (32 I + i, 32 J + j), i, j in [-H, 32).  Halo nodes come from the
-        // neighbours' results; nodes that do not exist or lie outside the band are +inf (a move from them never wins).
-        for (int e = tid; e < CS_W * CS_W + 2; e += TT_THREADS) cs[e] = inf;
-        __syncthreads();
-        {
-            // halo positions: H rows above (H x (32 + H)), then H columns to the left (32 x H); <= 3 per thread, their
-            // loads in flight together
-            const int ntop = H * (TL + H), nhalo = ntop + TL * H;
-            unsigned long long hv[3];
-            int hp[3];
-#pragma unroll
-            for (int u = 0; u < 3; u++) {
-                const int h = tid + u * TT_THREADS;
-                hp[u] = -1;
-                hv[u] = 0;
-                if (h < nhalo) {
-                    int ii, jj;
-                    if (h < ntop) { ii = h / (TL + H) - H; jj = h % (TL + H) - H; }
-                    else { ii = (h - ntop) / H; jj = (h - ntop) % H - H; }
-                    const int xx = TL * I + ii, yy = TL * J + jj;
-                    if (xx >= 0 && yy >= 0 && xx <= xs && yy <= ys) {
-                        const int a = xx + yy, b = yy - bo_l[a - abase];
-                        if (b >= 0 && b < B) {
-                            // (a neighbour's value: stored sc1 and drained before its flag, so an sc1 load behind the flag
-                            //  poll sees it without an agent-scope acquire: MI355X_MICROARCH.md, hand-offs with sc1 loads)
-                            hp[u] = (ii + TT_HALO) * CS_W + (jj + TT_HALO);
-                            hv[u] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(Lv.csum) + ((size_t)a * B + b),
-                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 3; u++)
-                if (hp[u] >= 0) cs[hp[u]] = __longlong_as_double((long long)hv[u]);
-        }
-        __syncthreads();
+        tile_halo_fill<false, 3>(cs, CS_W * CS_W + 2, geo, band, Lv.csum, I, J);
         stamp(3);
         // ---- phase 3: the tile's 63 node anti-diagonals, all four waves: thread = (node j = tid >> 3, move slot = tid & 7).
         // A slot relaxes the moves t = slot, slot + 8, ... (kept in registers, unrolled) with every csum / cost read of the
@@ -342,23 +264,7 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
                     best.tot = take ? tot : best.tot;
                     best.key = take ? m_key[m] : best.key;
                 }
-                // merge over the node's eight lanes: lane ^ 1, lane ^ 2 (quad permutes), then the other quad (half-row mirror);
-                // (total, move index) order without a short-circuit branch
-#define TILE_MERGE(CTRL)                                                                                                      \
-    {                                                                                                                         \
-        const unsigned long long u_ = __double_as_longlong(best.tot);                                                         \
-        const unsigned lo_ = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u_, CTRL, 0xf, 0xf, true);                      \
-        const unsigned hi_ = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u_ >> 32), CTRL, 0xf, 0xf, true);              \
-        const int ok_ = __builtin_amdgcn_mov_dpp(best.key, CTRL, 0xf, 0xf, true);   /* (every lane has a source: no old value) */ \
-        const double ot_ = __longlong_as_double(((unsigned long long)hi_ << 32) | lo_);                                       \
-        const bool tk_ = (ot_ < best.tot) | ((ot_ == best.tot) & (ok_ < best.key));                                           \
-        best.tot = tk_ ? ot_ : best.tot;                                                                                      \
-        best.key = tk_ ? ok_ : best.key;                                                                                      \
-    }
-                TILE_MERGE(0xB1)   // quad_perm [1,0,3,2]
-                TILE_MERGE(0x4E)   // quad_perm [2,3,0,1]
-                TILE_MERGE(0x141)  // row_half_mirror: lane k of an 8-lane group <-> lane 7 - k (the other quad)
-#undef TILE_MERGE
+                node_merge(best);   // over the node's eight lanes
                 const bool won = general & (best.tot < inf);
                 double v = won ? best.tot : inf;
                 int bpv = won ? (((best.key & 255) << 4) | ((best.key >> 8) & 255)) : 0xFF;
@@ -376,30 +282,8 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles(const SvxPairDev* __r
         }
         __syncthreads();
         stamp(4);
-        // ---- phase 4: results into the node arrays.  What the neighbours read (the last H rows and columns) goes first,
-        // sc1 and drained, then the flag; the interior follows with plain stores (only the traceback kernel reads it).
-        auto store_nodes = [&](bool edge) {
-            for (int e = tid; e < TL * TL; e += TT_THREADS) {
-                const int i = e / TL, j2 = e % TL;
-                if ((i >= TL - H || j2 >= TL - H) != edge) continue;
-                const int xx = TL * I + i, yy = TL * J + j2;
-                if (xx > xs || yy > ys) continue;
-                const int a = xx + yy, b = yy - bo_l[a - abase];
-                if (b < 0 || b >= B) continue;
-                const size_t o = (size_t)a * B + b;
-                const double v = cs[(i + TT_HALO) * CS_W + (j2 + TT_HALO)];
-                if (edge) __hip_atomic_store(reinterpret_cast<unsigned long long*>(Lv.csum) + o, (unsigned long long)__double_as_longlong(v),
-                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else Lv.csum[o] = v;
-                Lv.bpk[o] = bpt[e];
-            }
-        };
-        store_nodes(true);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(P.t_flag + P.t_pref[s] + (I - P.t_lo[s]), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        stamp(5);
-        store_nodes(false);
+        // ---- phase 4: results into the node arrays; the neighbours read the last H rows and columns
+        tile_publish<false>(cs, geo, band, Lv.csum, P.t_flag + tile_flag_at(P, s, I), I, J, stamp, [&](size_t o, int e) { Lv.bpk[o] = bpt[e]; });
     }
 }
 
@@ -466,17 +350,11 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_gen(const SvxPairDev*
 
     TileStamp stamp(prof);
     for (;;) {
-        __syncthreads();
-        stamp(6);
-        if (tid == 0) sh_ticket = atomicAdd(ticket, 1);
-        __syncthreads();
-        const int tk = sh_ticket;
-        if (tk >= total) break;
-        ecur = tile_entry(gpref, nent, tk, ecur);
-        const int s = (int)(ecur / n_pairs);
-        const SvxPairDev& P = pairs[ecur % n_pairs];
+        const TileAt at = tile_claim<false>(pairs, n_pairs, gpref, nent, total, ticket, &sh_ticket, ecur, stamp);
+        if (at.p < 0) break;
+        const int s = at.s, I = at.I, J = at.J;
+        const SvxPairDev& P = pairs[at.p];
         const SvxLevel& Lv = P.lev[0];
-        const int I = P.t_lo[s] + (tk - gpref[ecur]), J = s - I;
         const int xs = Lv.n[0], ys = Lv.n[1], d = P.d;
         const int rowbytes = d * (int)sizeof(St);
         const int NK = (rowbytes + TT_SLAB - 1) / TT_SLAB;
@@ -514,68 +392,17 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_gen(const SvxPairDev*
             });
         }
         const int abase = TL * s - HX - HY;
-        for (int i = tid; i < 2 * TL + HX + HY; i += TT_THREADS) {
-            const int a = abase + i;
-            bo_l[i] = (a >= 0 && a < A + 2) ? Lv.boff_out[a] : (1 << 28);
-        }
+        tile_band_offsets(bo_l, Lv.boff_out, abase, 2 * TL + HX + HY, A);
         __syncthreads();  // (also: the planes are written, and the ring is free for the csum tile)
         stamp(1);
         // ---- phase 2: wait for every band tile that holds halo nodes: rows I - ceil(Hx / 32) .. I, columns
-        // J - ceil(Hy / 32) .. J (all on earlier tile anti-diagonals: smaller tickets, running workgroups)
-        {
-            const int ri = (HX + TL - 1) / TL, rj = (HY + TL - 1) / TL;
-            const int nnb = (ri + 1) * (rj + 1) - 1;
-            for (int e = tid; e < nnb; e += TT_THREADS) {
-                const int ni = I - ri + e / (rj + 1), nj = J - rj + e % (rj + 1), ns = ni + nj;
-                if (ni < 0 || nj < 0) continue;
-                const int off = ni - P.t_lo[ns];
-                if (off < 0 || off >= P.t_cnt[ns]) continue;
-                const int* flag = P.t_flag + P.t_pref[ns] + off;
-                long spins = 0;
-                while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 && spins < (1l << 25)) {
-                    __builtin_amdgcn_s_sleep(2);
-                    spins++;
-                }
-                if (spins >= (1l << 25)) *P.status = SVX_ERR_HIP;
-            }
-        }
-        __syncthreads();
+        // J - ceil(Hy / 32) .. J (all on earlier tile anti-diagonals: smaller tickets, running workgroups), then the halo into
+        // the csum tile: position (i + Hx, j + Hy) <-> node (32 I + i, 32 J + j), i in [-Hx, 32), j in [-Hy, 32)
+        const TileBand band{xs, ys, B, abase, bo_l};
+        const TileGeo geo{HX, HY, CSY, HX, HY};
+        tile_wait<false>(P, P.t_flag, I, J, (HX + TL - 1) / TL, (HY + TL - 1) / TL);
         stamp(2);
-        // csum tile: position (i + Hx, j + Hy) <-> node (32 I + i, 32 J + j), i in [-Hx, 32), j in [-Hy, 32)
-        for (int e = tid; e <= NCS; e += TT_THREADS) cs[e] = inf;
-        __syncthreads();
-        {
-            const int ntop = HX * CSY, nhalo = ntop + TL * HY;
-            for (int h0 = 0; h0 < nhalo; h0 += 4 * TT_THREADS) {
-                unsigned long long hv[4];
-                int hp[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int h = h0 + tid + u * TT_THREADS;
-                    hp[u] = -1;
-                    hv[u] = 0;
-                    if (h < nhalo) {
-                        int ii, jj;
-                        if (h < ntop) { ii = h / CSY - HX; jj = h % CSY - HY; }
-                        else { ii = (h - ntop) / HY; jj = (h - ntop) % HY - HY; }
-                        const int xx = TL * I + ii, yy = TL * J + jj;
-                        if (xx >= 0 && yy >= 0 && xx <= xs && yy <= ys) {
-                            const int a = xx + yy, b = yy - bo_l[a - abase];
-                            if (b >= 0 && b < B) {
-                                // (sc1 stores drained before the neighbour's flag; sc1 loads behind the flag poll)
-                                hp[u] = (ii + HX) * CSY + (jj + HY);
-                                hv[u] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(Lv.csum) + ((size_t)a * B + b),
-                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (hp[u] >= 0) cs[hp[u]] = __longlong_as_double((long long)hv[u]);
-            }
-        }
-        __syncthreads();
+        tile_halo_fill<false, 4>(cs, NCS + 1, geo, band, Lv.csum, I, J);
         stamp(3);
         // ---- phase 3: the tile's 63 node anti-diagonals; thread = (node column j, move slot), MS moves per slot in
         // registers, merged by (total, move index) over the node's eight lanes as in k_band_tiles.  The costs of
@@ -633,21 +460,7 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_gen(const SvxPairDev*
                     best.tot = take ? tot : best.tot;
                     best.key = take ? m_key[m] : best.key;
                 }
-#define TILE_MERGE(CTRL)                                                                                                      \
-    {                                                                                                                         \
-        const unsigned long long u_ = __double_as_longlong(best.tot);                                                         \
-        const unsigned lo_ = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u_, CTRL, 0xf, 0xf, true);                      \
-        const unsigned hi_ = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u_ >> 32), CTRL, 0xf, 0xf, true);              \
-        const int ok_ = __builtin_amdgcn_mov_dpp(best.key, CTRL, 0xf, 0xf, true);                                             \
-        const double ot_ = __longlong_as_double(((unsigned long long)hi_ << 32) | lo_);                                       \
-        const bool tk_ = (ot_ < best.tot) | ((ot_ == best.tot) & (ok_ < best.key));                                           \
-        best.tot = tk_ ? ot_ : best.tot;                                                                                      \
-        best.key = tk_ ? ok_ : best.key;                                                                                      \
-    }
-                TILE_MERGE(0xB1)
-                TILE_MERGE(0x4E)
-                TILE_MERGE(0x141)
-#undef TILE_MERGE
+                node_merge(best);
                 const bool won = general & (best.tot < inf);
                 double v = won ? best.tot : inf;
                 int bpv = won ? (best.key & 0xFFFF) : 0xFFFF;
@@ -670,36 +483,17 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_gen(const SvxPairDev*
         }
         __syncthreads();
         stamp(4);
-        // ---- phase 4: what later tiles read (the last Hx rows and the last Hy columns; all of the tile once a step
-        // reaches 32) sc1 and drained, then the flag; the interior follows with plain stores
-        auto store_nodes = [&](bool edge) {
-            for (int e = tid; e < TL * TL; e += TT_THREADS) {
-                const int i = e / TL, j2 = e % TL;
-                if ((i >= TL - HX || j2 >= TL - HY) != edge) continue;
-                const int xx = TL * I + i, yy = TL * J + j2;
-                if (xx > xs || yy > ys) continue;
-                const int a = xx + yy, b = yy - bo_l[a - abase];
-                if (b < 0 || b >= B) continue;
-                const size_t o = (size_t)a * B + b;
-                const double v = cs[(i + HX) * CSY + (j2 + HY)];
-                if (edge) __hip_atomic_store(reinterpret_cast<unsigned long long*>(Lv.csum) + o, (unsigned long long)__double_as_longlong(v),
-                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else Lv.csum[o] = v;
-                const int bv = bpt[e];
-                if (Lv.bpk) {
-                    Lv.bpk[o] = bv == 0xFFFF ? (unsigned char)0xFF : (unsigned char)(((bv & 255) << 4) | (bv >> 8));
-                } else {
-                    Lv.xp[o] = bv == 0xFFFF ? -42 : (bv & 255);
-                    Lv.yp[o] = bv == 0xFFFF ? -42 : (bv >> 8);
-                }
+        // ---- phase 4: results into the node arrays; later tiles read the last Hx rows and the last Hy columns (all of the
+        // tile once a step reaches 32)
+        tile_publish<false>(cs, geo, band, Lv.csum, P.t_flag + tile_flag_at(P, s, I), I, J, stamp, [&](size_t o, int e) {
+            const int bv = bpt[e];
+            if (Lv.bpk) {
+                Lv.bpk[o] = bv == 0xFFFF ? (unsigned char)0xFF : (unsigned char)(((bv & 255) << 4) | (bv >> 8));
+            } else {
+                Lv.xp[o] = bv == 0xFFFF ? -42 : (bv & 255);
+                Lv.yp[o] = bv == 0xFFFF ? -42 : (bv >> 8);
             }
-        };
-        store_nodes(true);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(P.t_flag + P.t_pref[s] + (I - P.t_lo[s]), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        stamp(5);
-        store_nodes(false);
+        });
     }
 }
 
@@ -801,12 +595,9 @@ int svxl_band_tiles_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, co
     // one persistent workgroup per CU (> 100 KB of LDS each): all of them are resident, so a workgroup that waits for
     // a neighbour's flag always waits for a running workgroup
     dim3 grid((unsigned)ncu);
-    const char* penv = getenv("SVX_TILE_PROF");
-    unsigned long long* prof = nullptr;
-    if (penv && atoi(penv) != 0) {
-        SVX_HIP(ctx, hipMalloc(&prof, 8 * sizeof(unsigned long long)));
-        SVX_HIP(ctx, hipMemsetAsync(prof, 0, 8 * sizeof(unsigned long long), st));
-    }
+    TileProf tp;
+    if (const int rc = tp.begin(ctx, st, "wide band")) return rc;
+    unsigned long long* prof = tp.dev;
     // general shape: moves per DP slot MS = ceil((T + 2) / 8), rounded up to an instantiated count
     const int ms_need = (types.n + 2 + 7) / 8;
     static const int ms_set[] = {2, 3, 4, 6, 9, 17};
@@ -826,21 +617,15 @@ int svxl_band_tiles_batch(svx_ctx* ctx, const SvxPairDev* pairs, int n_pairs, co
         else if (ms == 9) GEN(E, 9, false);                                                                                        \
         else GEN(E, 17, false);                                                                                                    \
     } while (0)
-    if (dtype == SVX_F32) TILES(ElemF32);
-    else if (dtype == SVX_F16) TILES(ElemF16);
-    else TILES(ElemBF16);
+    SVX_TILE_BY_DTYPE(dtype, TILES);
 #undef TILES
 #undef GEN
-    SVX_LAUNCH_CHECK(ctx, "k_band_tiles");
+    const hipError_t le = hipGetLastError(), re = tp.end(st, le);
+    if (le != hipSuccess) return svx_fail(ctx, SVX_ERR_HIP, "launch %s: %s", "k_band_tiles", hipGetErrorString(le));
+    if (re != hipSuccess) return svx_fail(ctx, SVX_ERR_HIP, "wide band: tile profile read-back: %s", hipGetErrorString(re));
     if (prof) {
-        unsigned long long h[8];
-        SVX_HIP(ctx, hipMemcpyAsync(h, prof, sizeof(h), hipMemcpyDeviceToHost, st));
-        SVX_HIP(ctx, hipStreamSynchronize(st));
-        (void)hipFree(prof);
-        static const char* nm[7] = {"ticket+lookup", "costs", "wait", "halo", "cs-init..dp-start", "store+flag", "interior-store+loop"};
-        // (slot 3 = halo fill, slot 4 = the DP sweep; names follow the stamps' positions)
-        fprintf(stderr, "[svx tile sweep, summed over %d workgroups, ms]", ncu);
-        for (int i = 0; i < 7; i++) fprintf(stderr, " p%d(%s)=%.2f", i, nm[i], (double)h[i] * 1e-5);
+        static const char* const nm[7] = {"ticket+lookup", "costs", "wait", "clear+halo", "dp", "edge-store+flag", "interior-store+loop"};
+        tp.print("svx tile sweep", grid.x, nm);
         if (shape == 2) {
             int streamed = 0;
             for (int g = 0; g < gplan.ng; g++) streamed += gplan.g[g].nslot;

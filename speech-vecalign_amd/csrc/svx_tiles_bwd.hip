@@ -29,7 +29,9 @@
 //                     (tile, cut) on a monotone integer image of the double goes to cutmin.
 //   k_slack_wide      per pair: slack[r] = cutmin[c] - total for the rows that are edges, NaN otherwise; the summary.
 // The tile plan (t_lo, t_cnt, t_pref, the ticket table) is the forward call's, still in its arena; flags are an array of
-// this call's own.  Plain C++ and vector stores only.
+// this call's own.  Claim, wait, halo fill and publish are the scaffold of svx_tile_plan.h with BWD = true; this file holds
+// the cost phase, the F and path fill, the node-diagonal loop with the cut fold, and the cut minima.  Plain C++ and vector
+// stores only.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -47,36 +49,18 @@ __device__ __forceinline__ double cut_value(unsigned long long k) {   // all one
     return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
-__device__ __forceinline__ double dpp_f64(double v, int which) {
-    const unsigned long long u = __double_as_longlong(v);
-    unsigned lo, hi;
-    if (which == 0) {        // quad_perm [1,0,3,2]
-        lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u, 0xB1, 0xf, 0xf, true);
-        hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u >> 32), 0xB1, 0xf, 0xf, true);
-    } else if (which == 1) { // quad_perm [2,3,0,1]
-        lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u, 0x4E, 0xf, 0xf, true);
-        hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u >> 32), 0x4E, 0xf, 0xf, true);
-    } else if (which == 2) { // row_half_mirror
-        lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u, 0x141, 0xf, 0xf, true);
-        hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u >> 32), 0x141, 0xf, 0xf, true);
-    } else {                 // row_mirror
-        lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u, 0x140, 0xf, 0xf, true);
-        hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u >> 32), 0x140, 0xf, 0xf, true);
-    }
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 __device__ __forceinline__ double min_f64(double a, double b) { return b < a ? b : a; }
 // minimum over a node's eight lanes (every lane ends with it)
 __device__ __forceinline__ double node_min(double v) {
-    v = min_f64(v, dpp_f64(v, 0));
-    v = min_f64(v, dpp_f64(v, 1));
-    v = min_f64(v, dpp_f64(v, 2));
+    v = min_f64(v, dpp_f64<DPP_QUAD_1032>(v));
+    v = min_f64(v, dpp_f64<DPP_QUAD_2301>(v));
+    v = min_f64(v, dpp_f64<DPP_HALF_MIRROR>(v));
     return v;
 }
 // minimum over the wave (every lane ends with it): the exchanges of wave_max (svx_common.h) on the two halves of a double
 __device__ __forceinline__ double wave_min_f64(double v, int lane) {
     v = node_min(v);
-    v = min_f64(v, dpp_f64(v, 3));
+    v = min_f64(v, dpp_f64<DPP_ROW_MIRROR>(v));
     {
         const unsigned long long u = __double_as_longlong(v);
         const unsigned lo = xchg16_u32((unsigned)u, lane), hi = xchg16_u32((unsigned)(u >> 32), lane);
@@ -142,30 +126,17 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_bwd(const SvxPairDev*
     const int total = gpref[nent];
     for (int t = tid; t < NTt; t += TT_THREADS) tpk[t] = (int)ty.x[t] | ((int)ty.y[t] << 8);
     const double inf = __builtin_inf();
-    long long ecur = nent - 1;  // reverse tickets: the (diagonal, pair) entry of a workgroup's ticket only moves backward
+    long long ecur = nent - 1;
 
     TileStamp stamp(prof);
     for (;;) {
-        __syncthreads();  // the previous tile is finished with LDS
-        stamp(6);
-        if (tid == 0) sh_ticket = atomicAdd(ticket, 1);
-        __syncthreads();
-        if (sh_ticket >= total) break;
-        const int tk = total - 1 - sh_ticket;
-        {   // the last entry e <= ecur with gpref[e] <= tk (gpref[0] = 0)
-            long long lo = 0, hi = ecur;
-            while (lo < hi) {
-                const long long mid = (lo + hi + 1) >> 1;
-                if (gpref[mid] <= tk) lo = mid; else hi = mid - 1;
-            }
-            ecur = lo;
-        }
-        const int s = (int)(ecur / n_pairs);
-        const SvxPairDev& P = pairs[ecur % n_pairs];
-        const BwdPair Q = bw[ecur % n_pairs];
+        const TileAt at = tile_claim<true>(pairs, n_pairs, gpref, nent, total, ticket, &sh_ticket, ecur, stamp);
+        if (at.p < 0) break;
+        const int s = at.s, I = at.I, J = at.J;
+        const SvxPairDev& P = pairs[at.p];
+        const BwdPair Q = bw[at.p];
         if (!Q.slack) continue;   // (uniform) a skipped pair: none of its tiles waits for another
         const SvxLevel& Lv = P.lev[0];
-        const int I = P.t_lo[s] + (tk - gpref[ecur]), J = s - I;
         const int xs = Lv.n[0], ys = Lv.n[1], d = P.d;
         const int rowbytes = d * (int)sizeof(St);
         const int NK = (rowbytes + TT_SLAB - 1) / TT_SLAB;
@@ -193,48 +164,24 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_bwd(const SvxPairDev*
         R::store_scalars(snrm, sinv, tid, r_nrm, r_inv);
         // band offsets of the node diagonals this tile and its halo touch: a in [32 s, 32 s + 62 + 2 H]
         const int abase = TL * s;
-        for (int i = tid; i < 2 * TL + 2 * H; i += TT_THREADS) {
-            const int a = abase + i;
-            bo_l[i] = (a < A + 2) ? Lv.boff_out[a] : (1 << 28);  // (no such diagonal: nothing is in its band)
-        }
+        tile_band_offsets(bo_l, Lv.boff_out, abase, 2 * TL + 2 * H, A);
         __syncthreads();
         tile_cost_planes<UPW, 1>(acc, nunits, wave, lane, snrm, sinv, [&](int tl) {
             return TilePlane{tpk[tl] & 255, tpk[tl] >> 8, (plan.type_slots[tl] & 255) * TL, (plan.type_slots[tl] >> 8) * TL, planes + tl * TL * TL};
         });
         stamp(1);
-        // ---- phase 2: wait for the neighbours below and to the right (all three, when they exist, have smaller reverse tickets)
-        if (tid == 0) {
-            const int nb[3][2] = {{I + 1, J}, {I, J + 1}, {I + 1, J + 1}};
-            for (int e = 0; e < 3; e++) {
-                const int ni = nb[e][0], nj = nb[e][1], ns = ni + nj;
-                if (ns >= P.t_nd) continue;
-                const int off = ni - P.t_lo[ns];
-                if (off < 0 || off >= P.t_cnt[ns]) continue;  // not a band tile: nothing to wait for
-                const int* flag = Q.flag + P.t_pref[ns] + off;
-                // (bounded: the neighbour's workgroup is running; the bound only turns a programming error into an error code)
-                long spins = 0;
-                while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 && spins < (1l << 25)) {
-                    __builtin_amdgcn_s_sleep(2);
-                    spins++;
-                }
-                if (spins >= (1l << 25)) *P.status = SVX_ERR_HIP;
-            }
-        }
-        __syncthreads();
+        // ---- phase 2: wait for the neighbours below and to the right (all three, when they exist, have smaller reverse
+        // tickets), then their halo into the Bk tile: position (i, j) <-> node (32 I + i, 32 J + j), i, j in [0, 32 + H)
+        // (the hand-off: svx_tile_plan.h)
+        const TileBand band{xs, ys, B, abase, bo_l};
+        const TileGeo geo{H, H, CS_W, 0, 0};
+        tile_wait<true>(P, Q.flag, I, J, 1, 1);
         stamp(2);
-        // Bk tile: position (i, j) <-> node (32 I + i, 32 J + j), i, j in [0, 32 + H).  Halo nodes come from the neighbours'
-        // results; nodes that do not exist or lie outside the band are +inf (a move into them never wins).
-        for (int e = tid; e < CS_W * CS_W + 2; e += TT_THREADS) cs[e] = inf;
         // F of the tile's own nodes (plain loads: the forward sweep is complete), the path's node of its diagonals
+        // (in front of the halo fill, whose barriers cover these writes too)
         for (int e = tid; e < TL * TL; e += TT_THREADS) {
-            const int i = e / TL, j2 = e % TL;
-            const int xx = TL * I + i, yy = TL * J + j2;
-            double f = inf;
-            if (xx <= xs && yy <= ys) {
-                const int a = xx + yy, b = yy - bo_l[a - abase];
-                if (b >= 0 && b < B) f = gld(Lv.csum + ((size_t)a * B + b));
-            }
-            fs[e] = f;
+            size_t o;
+            fs[e] = band.cell(TL * I + e / TL, TL * J + e % TL, &o) ? gld(Lv.csum + o) : inf;
         }
         if (tid < 64) {
             const int a = abase + tid;
@@ -242,39 +189,7 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_bwd(const SvxPairDev*
             pth[2 * tid] = has ? gld(Q.tab + 2 * (size_t)a) : -1;
             pth[2 * tid + 1] = has ? gld(Q.tab + 2 * (size_t)a + 1) : -1;
         }
-        __syncthreads();
-        {
-            // halo positions: H rows below (H x (32 + H)), then H columns to the right (32 x H); <= 3 per thread
-            const int nbot = H * (TL + H), nhalo = nbot + TL * H;
-            unsigned long long hv[3];
-            int hp[3];
-#pragma unroll
-            for (int u = 0; u < 3; u++) {
-                const int h = tid + u * TT_THREADS;
-                hp[u] = -1;
-                hv[u] = 0;
-                if (h < nhalo) {
-                    int ii, jj;
-                    if (h < nbot) { ii = TL + h / (TL + H); jj = h % (TL + H); }
-                    else { ii = (h - nbot) / H; jj = TL + (h - nbot) % H; }
-                    const int xx = TL * I + ii, yy = TL * J + jj;
-                    if (xx <= xs && yy <= ys) {
-                        const int a = xx + yy, b = yy - bo_l[a - abase];
-                        if (b >= 0 && b < B) {
-                            // (a neighbour's value: stored sc1 and drained before its flag, so an sc1 load behind the flag
-                            //  poll sees it without an agent-scope acquire: the hand-off of svx_tiles.hip)
-                            hp[u] = ii * CS_W + jj;
-                            hv[u] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(Q.bsum) + ((size_t)a * B + b),
-                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 3; u++)
-                if (hp[u] >= 0) cs[hp[u]] = __longlong_as_double((long long)hv[u]);
-        }
-        __syncthreads();
+        tile_halo_fill<true, 3>(cs, CS_W * CS_W + 2, geo, band, Q.bsum, I, J);
         stamp(3);
         // ---- phase 3: the tile's 63 node anti-diagonals from the last to the first, all four waves: thread = (node j = tid >> 3,
         // move slot = tid & 7); a slot relaxes the moves t = slot, slot + 8, ... OUT of its node.  Successors outside the
@@ -401,29 +316,8 @@ __global__ __launch_bounds__(TT_THREADS) void k_band_tiles_bwd(const SvxPairDev*
             if (m < inf && c < A + 2)
                 __hip_atomic_fetch_min(Q.cutmin + c, cut_image(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        // ---- phase 4: Bk into the plane.  What the neighbours read (the first H rows and columns) goes first, sc1 and
-        // drained, then the flag; the interior follows with plain stores
-        auto store_nodes = [&](bool edge) {
-            for (int e = tid; e < TL * TL; e += TT_THREADS) {
-                const int i = e / TL, j2 = e % TL;
-                if ((i < H || j2 < H) != edge) continue;
-                const int xx = TL * I + i, yy = TL * J + j2;
-                if (xx > xs || yy > ys) continue;
-                const int a = xx + yy, b = yy - bo_l[a - abase];
-                if (b < 0 || b >= B) continue;
-                const size_t o = (size_t)a * B + b;
-                const double v = cs[i * CS_W + j2];
-                if (edge) __hip_atomic_store(reinterpret_cast<unsigned long long*>(Q.bsum) + o, (unsigned long long)__double_as_longlong(v),
-                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else Q.bsum[o] = v;
-            }
-        };
-        store_nodes(true);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(Q.flag + P.t_pref[s] + (I - P.t_lo[s]), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        stamp(5);
-        store_nodes(false);
+        // ---- phase 4: Bk into the plane; the neighbours read the first H rows and columns
+        tile_publish<true>(cs, geo, band, Q.bsum, Q.flag + tile_flag_at(P, s, I), I, J, stamp, [](size_t, int) {});
     }
 }
 
@@ -478,42 +372,26 @@ int svxl_band_tiles_bwd(svx_ctx* ctx, const SvxPairDev* pairs, const BwdPair* bw
     hipLaunchKernelGGL(k_bwd_table, dim3(n_pairs), dim3(256), 0, st, pairs, bw);
     SVX_LAUNCH_CHECK(ctx, "k_bwd_table");
     dim3 grid((unsigned)tile_cu_count());   // one persistent workgroup per CU, all resident (> 100 KB of LDS each)
-    const char* penv = getenv("SVX_TILE_PROF");
-    unsigned long long* prof = nullptr;
-    if (penv && atoi(penv) != 0) {
-        SVX_HIP(ctx, hipMalloc(&prof, 8 * sizeof(unsigned long long)));
-        const hipError_t me = hipMemsetAsync(prof, 0, 8 * sizeof(unsigned long long), st);
-        if (me != hipSuccess) {
-            (void)hipFree(prof);
-            return svx_fail(ctx, SVX_ERR_HIP, "svx_row_slack_wide: hipMemsetAsync: %s", hipGetErrorString(me));
-        }
-    }
+    TileProf tp;
+    if (const int rc = tp.begin(ctx, st, "svx_row_slack_wide")) return rc;
+    unsigned long long* prof = tp.dev;
 #define TILES(E)                                                                                                                   \
     do {                                                                                                                           \
         if (shape == 0) hipLaunchKernelGGL((k_band_tiles_bwd<E, 8, 5, 5>), grid, dim3(TT_THREADS), 0, st, pairs, bw, n_pairs, types, plan, W, max_nd, gpref, ticket, prof); \
         else hipLaunchKernelGGL((k_band_tiles_bwd<E, 12, 8, 2>), grid, dim3(TT_THREADS), 0, st, pairs, bw, n_pairs, types, plan, W, max_nd, gpref, ticket, prof); \
     } while (0)
-    if (dtype == SVX_F32) TILES(ElemF32);
-    else if (dtype == SVX_F16) TILES(ElemF16);
-    else TILES(ElemBF16);
+    SVX_TILE_BY_DTYPE(dtype, TILES);
 #undef TILES
     hipError_t le = hipGetLastError();
     if (le == hipSuccess) {
         hipLaunchKernelGGL(k_slack_wide, dim3(n_pairs), dim3(256), 0, st, pairs, bw, types, 2 * W);
         le = hipGetLastError();
     }
-    unsigned long long h[8] = {0};
-    if (prof) {   // (read and freed whatever the launches said: the buffer does not outlive the call)
-        if (le == hipSuccess) le = hipMemcpyAsync(h, prof, sizeof(h), hipMemcpyDeviceToHost, st);
-        const hipError_t se = hipStreamSynchronize(st);
-        if (le == hipSuccess) le = se;
-        (void)hipFree(prof);
-    }
+    le = tp.end(st, le);
     if (le != hipSuccess) return svx_fail(ctx, SVX_ERR_HIP, "svx_row_slack_wide: backward tile sweep: %s", hipGetErrorString(le));
     if (prof) {
-        static const char* nm[7] = {"ticket+lookup", "costs", "wait", "F+halo", "dp+cuts", "cutmin+store+flag", "interior-store+loop"};
-        fprintf(stderr, "[svx backward tile sweep, summed over %u workgroups, ms]", grid.x);
-        for (int i = 0; i < 7; i++) fprintf(stderr, " p%d(%s)=%.2f", i, nm[i], (double)h[i] * 1e-5);
+        static const char* const nm[7] = {"ticket+lookup", "costs", "wait", "F+halo", "dp+cuts", "cutmin+store+flag", "interior-store+loop"};
+        tp.print("svx backward tile sweep", grid.x, nm);
         fprintf(stderr, "\n");
     }
     return SVX_OK;

@@ -139,6 +139,52 @@ def test_around_wide_bent_band_with_a_failed_pair():
     check_exact(pb, refs, "around_wide", failed=(1,))
 
 
+RAGGED = [(150, 137), (70, 90), (40, 200)]
+
+
+@pytest.mark.parametrize("a", [5, 6])
+def test_ragged_batch_with_the_middle_pair_skipped(a):
+    """Three pairs of different sizes in one batch (9, 5 and 8 tile anti-diagonals: the ticket table is ragged), on both
+    LDS-resident shapes.  All three measured: slack_ref, bit for bit.  Then svx_row_slack_wide with the middle pair's
+    slack NULL: pairs 0 and 2 get the bits they get when each is aligned and measured alone, and nothing of the middle
+    pair is written (its tiles are claimed and dropped, and the reverse entry lookup walks across them)."""
+    import ctypes
+    import torch
+    from svx import _lib
+    types, W, SENT, ISENT = alignment_types(a), 40, -7.0, -9
+    nd = [(n + 32) // 32 + (m + 32) // 32 - 1 for n, m in RAGGED]       # tile anti-diagonals that hold nodes 0 .. n, 0 .. m
+    assert sorted(nd) == [5, 8, 9]
+    pairs, refs = z_case(RAGGED, types, W, "f32", dp_ref.LEVELS2, 57 + a)
+    alone = {}
+    for i in (0, 2):
+        one = z_batch([pairs[i]], types, W, "f32")
+        one.run()
+        sl, sm = one.row_slack_wide()
+        one.ctx.sync()
+        alone[i] = (sl.cpu().numpy(), sm.cpu().numpy()[0].tolist())
+    pb = z_batch(pairs, types, W, "f32")
+    pb.run()
+    check_exact(pb, refs, "ragged_a%d" % a)
+    ctx = pb.ctx
+    slack = torch.full((int(pb.offs[-1]),), SENT, dtype=torch.float64, device="cuda")
+    summary = torch.full((3, 4), ISENT, dtype=torch.int32, device="cuda")
+    sw = (_lib.SlackWide * 3)()
+    for i in (0, 2):
+        sw[i].slack = slack.data_ptr() + 8 * int(pb.offs[i])
+    ctx.use_current_stream()
+    ctx.check(ctx.lib.svx_row_slack_wide(ctx.h, sw, ctypes.c_void_p(summary.data_ptr()), 3))
+    ctx.sync()
+    slack, summary = slack.cpu().numpy(), summary.cpu().numpy()
+    for i in (0, 2):
+        o, cap, (want, wsum) = int(pb.offs[i]), int(pb.offs[i + 1] - pb.offs[i]), alone[i]
+        rows = wsum[0]
+        assert 0 < rows <= cap and summary[i].tolist() == wsum
+        assert np.array_equal(slack[o:o + rows].view(np.int64), want[:rows].view(np.int64)), "pair %d: not the bits of the pair alone" % i
+        assert (slack[o + rows:o + cap] == SENT).all()
+    o, cap = int(pb.offs[1]), int(pb.offs[2] - pb.offs[1])
+    assert cap > 0 and (slack[o:o + cap] == SENT).all() and (summary[1] == ISENT).all()
+
+
 # ------------------------------------------------------------------------------------------ continuous data
 @functools.lru_cache(maxsize=None)
 def cost_bound(n, m, K, d, store, W, seed):
