@@ -46,7 +46,15 @@ enum svx_status {
  * Replaces nothing in the reference (its module is stateless); see SURVEY.md section 8(b). */
 int svx_create(int device_id, svx_ctx **out);
 int svx_destroy(svx_ctx *ctx);
-/* Use an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = default stream. */
+/* Use an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = default stream.
+ * The context carries state from call to call -- the arena, the post-processing scratch, the costs, sums and tile plan
+ * the "last call" entries read, the half-batches the pipeline holds back -- so a change of stream orders it: everything
+ * the context did under the old binding (a held-back half included: svx_flush runs first, under the old binding, so the
+ * stream a batch was launched on also sees its outputs complete) is ordered in front of the first work under the new
+ * one, by an event the new stream waits for; the host does not wait.  The handle that is already bound returns at once.
+ * A bound stream must stay alive until the context is bound elsewhere or destroyed.  What the caller still orders
+ * themselves: their own buffers across their own streams (inputs written on another stream than the one the call is
+ * bound to, outputs read on another one). */
 int svx_set_stream(svx_ctx *ctx, void *hip_stream);
 int svx_synchronize(svx_ctx *ctx);
 /* Message of the last failure on this context (ctx may be NULL for svx_create failures). */

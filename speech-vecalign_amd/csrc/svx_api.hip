@@ -99,6 +99,7 @@ struct svx_ctx_ext : svx_ctx {
     bool side_ready;
     int last_ntypes, last_band;  // of the last svx_align_batch call (svx_debug_level)
     bool last_ok;                // that call planned and launched everything: its descriptors hold device pointers (svx_band_contact)
+    hipEvent_t rebind;           // svx_set_stream: the old stream's work so far, which the new stream waits for (created on first use)
 };
 
 static inline svx_ctx_ext* X(svx_ctx* c) { return static_cast<svx_ctx_ext*>(c); }
@@ -180,6 +181,7 @@ int svx_create(int device_id, svx_ctx** out) {
     c->last_band = 0;
     c->last_ok = false;
     c->side_ready = false;
+    c->rebind = nullptr;
     *out = c;
     return SVX_OK;
 }
@@ -205,6 +207,7 @@ int svx_destroy(svx_ctx* ctx) {
     }
     if (c->chain_ready) (void)hipStreamDestroy(c->chain);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
+    if (c->rebind) (void)hipEventDestroy(c->rebind);
     for (int h = 0; h < 2; h++) {
         HalfState& H = c->half[h];
         if (H.arena) (void)hipFree(H.arena);
@@ -217,9 +220,20 @@ int svx_destroy(svx_ctx* ctx) {
     return SVX_OK;
 }
 
+// The context carries state from call to call (arena, post-processing scratch, the last run's planes, held-back halves),
+// so a change of stream orders everything done under the old binding in front of the first work under the new one.
 int svx_set_stream(svx_ctx* ctx, void* hip_stream) {
     if (!ctx) return SVX_ERR_ARG;
-    ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    if (s == ctx->stream) return SVX_OK;   // (the hot path never changes stream)
+    svx_ctx_ext* c = X(ctx);
+    SVX_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = svx_flush(ctx);   // held-back halves are launched, and their chains joined, on the stream their batch ran on
+    if (rc) return rc;
+    if (!c->rebind) SVX_HIP(ctx, hipEventCreateWithFlags(&c->rebind, hipEventDisableTiming));
+    SVX_HIP(ctx, hipEventRecord(c->rebind, ctx->stream));
+    SVX_HIP(ctx, hipStreamWaitEvent(s, c->rebind, 0));
+    ctx->stream = s;
     return SVX_OK;
 }
 
@@ -638,13 +652,15 @@ extern "C" int svx_debug_level(svx_ctx* ctx, int pair, int level, svx_level_view
     out->n0 = Lv.nrm[0]; out->n1 = Lv.nrm[1];
     out->del_penalty = Lv.pen;
     SVX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = svx_synchronize(ctx);  // (also launches what the pipeline still holds back)
+    int rc = svx_flush(ctx);  // (launches what the pipeline still holds back)
     if (rc) return rc;
-    if (Lv.n_align) SVX_HIP(ctx, hipMemcpy(&out->n_align, Lv.n_align, sizeof(int), hipMemcpyDeviceToHost));
-    out->alignments = Lv.align;
     const bool refined = (level < P.L) || (P.L == 0);
+    // the two counters: read on the context's stream, like svx_copy_to_host
+    if (Lv.n_align) SVX_HIP(ctx, hipMemcpyAsync(&out->n_align, Lv.n_align, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (refined) SVX_HIP(ctx, hipMemcpyAsync(&out->path_len, Lv.path_len, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    out->alignments = Lv.align;
     if (refined) {
-        SVX_HIP(ctx, hipMemcpy(&out->path_len, Lv.path_len, sizeof(int), hipMemcpyDeviceToHost));
         out->searchpath = Lv.path;
         out->a_b_costs = Lv.costs;
         out->b_offset = Lv.boff;

@@ -235,12 +235,28 @@ class Context:
         self.torch = torch
         self.tdev = torch.device("cuda", self.device)
         self.pipeline = False
+        # the stream handle use_current_stream() bound last (a new context is on the default stream, 0).  A caller who drives
+        # svx_set_stream through ctypes leaves it stale; the only consequence is one extra clearing of _held, after a
+        # flush the C side has done anyway
+        self._bound = 0
         self._held = []   # batches whose device work the pipeline may still hold back: kept alive until the next flush
         if os.environ.get("SVX_PIPELINE") == "1":   # default for this process (the GPU suite is also run once this way)
             self.set_pipeline(True)
 
     def use_current_stream(self):
-        self.lib.svx_set_stream(self.h, c_vp(self.torch.cuda.current_stream(self.tdev).cuda_stream))
+        """Bind torch's current stream (include/svx.h: svx_set_stream).  On a change the C side flushes the pipeline under
+        the old binding and makes the new stream wait for everything the context did on the old one."""
+        handle = int(self.torch.cuda.current_stream(self.tdev).cuda_stream)
+        self.check(self.lib.svx_set_stream(self.h, c_vp(handle)))   # (the same handle again: one pointer compare)
+        if handle != self._bound:
+            self._bound = handle
+            del self._held[:]   # flushed by the C side, as in flush()
+
+    def current(self):
+        """This context, bound to torch's current stream: the first line of every entry that launches on a context it did
+        not just take from context()."""
+        self.use_current_stream()
+        return self
 
     def check(self, rc):
         if rc != 0:
@@ -250,6 +266,7 @@ class Context:
             raise SvxError(rc, msg)
 
     def sync(self):
+        self.use_current_stream()
         self.check(self.lib.svx_synchronize(self.h))
         del self._held[:]
 
@@ -262,6 +279,7 @@ class Context:
         self.pipeline = bool(on)
 
     def flush(self):
+        self.use_current_stream()   # (a flush under another stream than the batch's: joined there, then this one waits)
         self.check(self.lib.svx_flush(self.h))
         # everything the pipeline held back is now ordered in front of whatever follows on the current stream, so memory
         # released from here on is reused behind it

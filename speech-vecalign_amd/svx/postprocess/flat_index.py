@@ -93,7 +93,7 @@ class FlatIndex:
 
     # -- population (prep_index.py:153-185: normalize_L2 + index.add per embedding file)
     def add(self, embed) -> None:
-        ctx = self.ctx
+        ctx = self.ctx.current()
         x = to_device_rows(ctx, embed)
         if x.ndim != 2 or x.shape[1] != self.d:
             raise ValueError(f"expected [n, {self.d}] rows, got {tuple(x.shape)}")
@@ -123,7 +123,7 @@ class FlatIndex:
 
     # -- search (score_align.py:137-148): mean cosine to the k nearest rows
     def mean_sim(self, queries, k: int):
-        ctx = self.ctx
+        ctx = self.ctx.current()
         q = to_device_rows(ctx, queries)
         if q.ndim != 2 or q.shape[1] != self.d:
             raise ValueError(f"expected [n, {self.d}] queries, got {tuple(q.shape)}")
@@ -137,7 +137,7 @@ class FlatIndex:
     def merge_topk(self, queries, k: int, topk=None, want_mean: bool = False):
         """One shard of a sharded search: merge this index's rows into the running top-k lists `topk` [n, k]
         (None: start them) -> (topk, mean_sim or None).  The shard may hold fewer than k rows, or none."""
-        ctx = self.ctx
+        ctx = self.ctx.current()
         t = ctx.torch
         q = to_device_rows(ctx, queries)
         if q.ndim != 2 or q.shape[1] != self.d:
@@ -162,7 +162,7 @@ class FlatIndex:
         query's list is ordered by (similarity descending, id ascending) and holds the first k of that order over all
         rows seen, (-inf, -1) where fewer than k were; shards may come in any order as long as their ids are distinct.
         The shard may hold fewer than k rows, or none."""
-        ctx = self.ctx
+        ctx = self.ctx.current()
         t = ctx.torch
         q = to_device_rows(ctx, queries)
         if q.ndim != 2 or q.shape[1] != self.d:
@@ -198,7 +198,7 @@ class FlatIndex:
         n_groups + 1 entries starting at 0 and never decreasing, q_off[-1] = the number of queries, db_off[-1] <= ntotal.
         -> (sims float32 [n, k], ids int64 [n, k]) device tensors; the ids are row numbers of this index, and the rows of
         group g equal, bit for bit, `search` of the group's queries in an index of the group's rows, plus db_off[g]."""
-        ctx = self.ctx
+        ctx = self.ctx.current()
         t = ctx.torch
         q = to_device_rows(ctx, queries)
         if q.ndim != 2 or q.shape[1] != self.d:

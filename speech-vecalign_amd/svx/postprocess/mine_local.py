@@ -143,6 +143,7 @@ def _unit_side(ctx, paths, use_stopes, fp16_embed, storage, pool):
     from .. import _lib
     from ..utils.embedding_utils import read_embeddings_pinned
     t = ctx.torch
+    ctx.use_current_stream()
     hosts = pool.map(lambda path: read_embeddings_pinned(path, use_stopes, fp16_embed), paths)
     if len({(h.dtype, h.shape[1]) for h in hosts}) != 1:
         raise ValueError("the embedding files of a batch differ in element type or dimension")

@@ -59,7 +59,7 @@ def margin_scores_device(idx_x: FlatIndex, idx_y: FlatIndex, x, y, k: int, margi
     """-> device float32 [n].  x, y: [n, d] numpy / torch rows in any of fp32 / fp16 / bf16 (not modified)."""
     if margin not in MARGINS:
         raise ValueError(f"Wrong margin type: {margin}")
-    ctx = idx_y.ctx
+    ctx = idx_y.ctx.current()
     xd, yd = to_device_rows(ctx, x), to_device_rows(ctx, y)
     assert xd.shape == yd.shape, f"{tuple(xd.shape)} {tuple(yd.shape)}"
     if yd.dtype != xd.dtype:
@@ -139,6 +139,7 @@ def global_margin_scores(x_local, y_local, k: int = 16, margin: str = "ratio", s
         totals.append(total)
     if min(totals) < k:
         raise ValueError(f"the corpus has {min(totals)} rows on one side, fewer than k = {k}")
+    ctx.use_current_stream()
     out = t.empty((xd.shape[0],), dtype=t.float32, device=ctx.tdev)
     ctx.check(ctx.lib.svx_margin_scores(ctx.h, ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(yd.data_ptr()),
                                         _torch_dtype_code(t, xd.dtype), int(xd.shape[0]), int(xd.shape[1]),
